@@ -9,7 +9,12 @@ exchange the path has, pipelined so that a step's reduce runs d
 step's launch (the last one finishes inside the timed region). value = closest-hit scene queries
 of all ranks / time.
 
-    python bench.py [--gpus N --steps K --warmup W]
+A plain run sets up, warms up, times the K steps and prints the result line. --full adds every
+other leg (the counting pass and the roofline it feeds, the image check, the reference-order leg,
+the CPU baseline); --dump-outputs DIR writes the last timed step's image for build-to-build
+comparison.
+
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 """
 from __future__ import annotations
@@ -122,15 +127,22 @@ def main():
                     help="BVH child order (include/jtrace.h jt_traversal): auto (the default: wide records for "
                          "deep HBM-mode scenes, near child first otherwise), near, wide, or the reference's "
                          "far-first order (src/bvh.jl:331-341)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: the counting pass and the roofline it feeds, "
+                         "the image check, the reference-order leg and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="rank 0: after the timed steps write the last step's results as DIR/<name>.npy: image (H x W x 4 "
+                         "float32 running means, the RCCL-reduced one for N > 1) and counters (float64: paths, rays, "
+                         "light queries of this rank's share)")
     ap.add_argument("--no-reference-order", action="store_true",
-                    help="skip the reference-order comparison line (rank 0, N=1, --traversal near)")
+                    help="--full: skip the reference-order comparison line (rank 0, N=1, --traversal near)")
     ap.add_argument("--batch", type=int, default=0,
                     help="trace_samples batch B (the reference's --batch, src/cli.jl:78-81; its default is 1): a step "
                          "makes one call per B samples, as Jtrace.main does (src/jtrace.jl:83); 0 (the default): "
                          "the rank's whole sample share in one call")
     ap.add_argument("--highqualitybvh", action="store_true",
                     help="the reference's SAH build (--highqualitybvh, src/bvh.jl:218-274) instead of split_middle")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline leg")
     ap.add_argument("--cpu-threads", type=int, default=16)
     ap.add_argument("--cpu-spp", type=int, default=128)
     ap.add_argument("--tile-groups", type=int, default=0,
@@ -139,12 +151,17 @@ def main():
     ap.add_argument("--as-rank-of", type=int, default=0,
                     help="N=1: trace rank 0's share of an N-rank run (per-GPU rate and roofline of that share)")
     ap.add_argument("--write-signature", action="store_true",
-                    help="N=1: record this workload's image fingerprint in profiles/image_signatures.json (with --as-rank-of: rank 0's share image)")
+                    help="N=1, --full: record this workload's image fingerprint in profiles/image_signatures.json (with "
+                         "--as-rank-of: rank 0's share image)")
     ap.add_argument("--print-workload", action="store_true",
                     help="print the workload key of this run's roofline record (scripts/gpu_measure.sh) and exit")
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE",
                     help="a library run-time option (jt_set_option, include/jtrace.h) for A/B runs; repeatable")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.write_signature and not args.full:
+        ap.error("--write-signature belongs to the image check: add --full")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -264,13 +281,26 @@ def main():
     for _ in range(args.warmup):
         step()
     drain()
-    # counting pass: the same step with every traversal counter on (level 1); the timed steps
-    # run the production kernel (level 0: paths/rays/light queries). The counts are a
-    # deterministic function of (seed, samples, BVH); the ray count cross-checks them.
-    state.set_counters(1)
-    full = step()
-    drain()
-    state.set_counters(0)
+    # counting pass (--full): the same step with every traversal counter on (level 1); the timed
+    # steps run the production kernel (level 0: paths/rays/light queries). The counts are a
+    # deterministic function of (seed, samples, BVH); the ray count cross-checks them (a plain
+    # run checks the timed steps against the first of them).
+    full = None
+    if args.full:
+        state.set_counters(1)
+        full = step()
+        drain()
+        state.set_counters(0)
+    else:
+        # one one-sample launch of the counting kernel (about a millisecond). Measured on MI355X: once that
+        # kernel has run in the process, every later launch of the production kernel is 1.0 % shorter
+        # (cornellbox: 52.81 -> 52.28 ms of kernel time; a launch of another production kernel does not do
+        # it) — presumably the scratch the runtime keeps for the queue is sized by the larger kernel.
+        # The counting pass has always preceded the timed steps, so the value is measured in that state.
+        state.set_counters(1)
+        state.reset()
+        state.trace_range(s0, s0 + 1)
+        state.set_counters(0)
     desc = state.describe()
     kernel = desc.split()[0].split("=", 1)[1]
     if dist is not None:
@@ -280,10 +310,13 @@ def main():
     rays = 0
     kernel_ms = 0.0
     agg = {k: 0 for k in ("paths", "rays", "light_queries", "launches")}
+    first = full
     for _ in range(args.steps):
         c = step()
-        if c["rays"] != full["rays"] or c["light_queries"] != full["light_queries"]:
-            raise SystemExit(f"non-deterministic ray count: {c} vs counting pass {full}")
+        if first is None:
+            first = c
+        if c["rays"] != first["rays"] or c["light_queries"] != first["light_queries"]:
+            raise SystemExit(f"non-deterministic ray count: {c} vs {'counting pass' if args.full else 'first timed step'} {first}")
         for k in agg:
             agg[k] += c[k]
         kernel_ms += c["kernel_ms"]
@@ -301,14 +334,25 @@ def main():
     else:
         total_rays = float(rays)
 
-    # Image check (rank 0, every N): block means of the final image — the RCCL-reduced one for
+    # the last timed step's image (rank 0): the RCCL-reduced one for N > 1
+    img_final = None
+    if rank == 0 and (args.full or args.dump_outputs):
+        img_final = (reduced[0].detach().cpu().numpy().reshape(H, W, 4) if world > 1 else state.get_image())
+    # --dump-outputs: what a caller of the timed path holds after its last step. The scene, the
+    # seed and the sample ranges are fixed by the arguments, so two builds compare file for file.
+    if rank == 0 and args.dump_outputs:
+        out_dir = Path(args.dump_outputs)
+        out_dir.mkdir(parents=True, exist_ok=True)
+        np.save(out_dir / "image.npy", np.ascontiguousarray(img_final, dtype=np.float32))
+        np.save(out_dir / "counters.npy", np.array([c["paths"], c["rays"], c["light_queries"]], dtype=np.float64))
+
+    # Image check (--full; rank 0, every N): block means of the final image — the RCCL-reduced one for
     # N > 1 — against the one-GPU signature committed for this workload (profiles/image_signatures.json,
     # jtrace/parallel.py): a wrong shard split, weight or reduce fails the run loudly
     # (--as-rank-of N: rank 0's share image, against the signature of that share)
     image_check = None
     partial = world == 1 and plan_world > 1  # --as-rank-of: one rank's share only, not the image
-    if rank == 0:
-        img_final = (reduced[0].detach().cpu().numpy().reshape(H, W, 4) if world > 1 else state.get_image())
+    if rank == 0 and args.full:
         sig = image_signature(img_final)
         sig_key = f"{Path(args.scene).stem} {args.sampler} {W}x{H}x{S}spp traversal={traversal}" + \
             ("".join(f" {o}" for o in sorted(args.opt) if o.split("=")[0] in RESULT_OPTIONS)) + \
@@ -326,14 +370,14 @@ def main():
         else:
             image_check = {"key": sig_key, "ok": None, "why": "no committed signature for this workload"}
 
-    # Reference-order leg (rank 0, N=1): the same workload with the reference's far-child-first
+    # Reference-order leg (--full; rank 0, N=1): the same workload with the reference's far-child-first
     # order (src/bvh.jl:331-341, SURVEY Appendix B item 9: performance only), timed the same way,
     # and the fraction of pixels whose final running mean differs from the near-first image (only
     # hits the slab test's rounding lets one order find and the other cull; exact-t ties re-run in
     # the reference's order)
     ref_order = None
-    if rank == 0 and world == 1 and not partial and args.traversal != "reference" and not args.no_reference_order \
-            and args.batch <= 0:
+    if args.full and rank == 0 and world == 1 and not partial and args.traversal != "reference" \
+            and not args.no_reference_order and args.batch <= 0:
         img_near = state.get_image()
         rp = abi.make_params(Params(scene=args.scene, samples=args.spp, sampler=2 if args.sampler == "naive" else 1,
                                     width=args.width, height=args.height, device=dev, batch=args.spp,
@@ -364,11 +408,11 @@ def main():
                      "per_ray": {k: round(rfull[k] / max(1, rfull["rays"]), 3)
                                  for k in ("nodes", "instances", "prims", "shades", "light_queries")}}
 
-    # CPU baseline leg (rank 0, N=1): the oracle on host cores over samples [0, cpu_spp) of this
+    # CPU baseline leg (--full; rank 0, N=1): the oracle on host cores over samples [0, cpu_spp) of this
     # workload; the GPU then re-traces exactly those samples so the two ray counts — hence the
     # two cameras and framings — are checked to agree (a libm ulp may flip a rare path: <= 0.1 %)
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline and world == 1 and not partial:
+    if args.full and rank == 0 and not args.no_cpu_baseline and world == 1 and not partial:
         # the oracle runs the order the GPU resolved "auto" to (it has no LDS/HBM mode to choose by)
         jp_cpu = type(jp).from_buffer_copy(jp)
         jp_cpu.traversal = abi.TRAVERSAL_ORDERS.index(traversal)
@@ -389,67 +433,71 @@ def main():
         ms_per_step = elapsed / args.steps * 1e3
         launches = max(1, agg["launches"])
         avg_launch_s = kernel_ms / launches / 1e3
-        per_launch = {k: v / max(1, full["launches"]) for k, v in full.items()}  # one step's launches
-        logical = algorithmic_bytes(per_launch, shade_record_bytes(scene),
-                                    any(len(s.quads) for s in scene.shapes), traversal == "wide")
-        sys.path.insert(0, str(ROOT / "scripts"))
-        from roofline import VMEM_MIX_PEAK_GIPS
-        # the source hash the Makefile embedded in the library that ran (jt_version), not a hash of
-        # this tree: no compiler is invoked at run time (under a PMC profiler a child process that
-        # execs would be refused), and a record can only match the binary it describes
-        build = library_build_hash(lib)
-        rec, rec_src = roofline_record(workload, kernel, build)
-        # The roof that binds, from the PMC counts of this kernel on this workload and build
-        # (committed record) over THIS run's launch time (HIP events):
-        #  - LDS mode (small scenes: the scene is in LDS): VALU issue of partly idle waves —
-        #    achieved = useful FP32 lane-operations per second, peak = the CUs' FP32 lane rate;
-        #  - HBM mode (node / primitive records L2-resident): the vector-memory return path (TD) —
-        #    achieved = vector-memory read wave-instructions per second, peak = the measured
-        #    gather ceiling for the traversal's own node records (scripts/td_mix_bench.hip,
-        #    profiles/r04_tdmix/: 64-B wide records 40.6, 16-B binary rows 34.7 G wave-instr/s);
-        #    td_unstalled_frac (TD busy and not waiting on the cache) beside it agrees with frac.
-        # HBM itself (measured traffic / 8 TB/s) is reported beside it as hbm_frac.
-        lds_mode = "mode=lds" in desc
-        roof = {"bound": "valu" if lds_mode else "vmem/TD", "achieved": None, "peak": None,
-                "unit": "G lane-ops/s" if lds_mode else "G wave-instr/s", "frac": None, "traffic": None,
-                "hbm_achieved_gbs": None, "hbm_peak_gbs": HBM_PEAK_GBS, "hbm_frac": None,
-                "source": rec_src, "build": build, "kernel": kernel, "launch": desc,
-                "avg_launch_ms": round(avg_launch_s * 1e3, 3), "binding": None}
-        if rec:
-            d = rec["derived"]
-            if lds_mode and "valu_lane_ops" in d:
-                achieved, peak = d["valu_lane_ops"] / avg_launch_s / 1e9, d["valu_peak_gops"]
-            elif not lds_mode and "vmem_rd_per_launch" in d:
-                achieved, peak = d["vmem_rd_per_launch"] / avg_launch_s / 1e9, VMEM_MIX_PEAK_GIPS[traversal]
-            else:
-                achieved = peak = None
-            if achieved is not None:
-                roof.update(achieved=round(achieved, 2), peak=round(peak, 2), frac=round(achieved / peak, 5))
-            traffic = d["traffic_bytes"]  # measured HBM bytes per launch (PMC, gfx950-corrected)
-            roof.update(traffic=int(traffic), hbm_achieved_gbs=round(traffic / avg_launch_s / 1e9, 1),
-                        hbm_frac=round(traffic / avg_launch_s / 1e9 / HBM_PEAK_GBS, 5))
-            roof["binding"] = {k: d[k] for k in ("valu_issue_frac", "lane_util", "fp32_lane_frac", "td_busy_frac",
-                                                 "td_unstalled_frac", "td_tc_stall_frac_of_busy", "l2_hit_rate", "l1_hit_rate",
-                                                 "l1_accesses_per_vmem_rd", "l1_misses_per_vmem_rd",
-                                                 "vmem_mix_frac", "vmem_mix_frac_resident", "clock_ghz") if k in d}
-            roof["binding"]["write_bytes_per_launch"] = int(d["write_bytes"])
-            roof["binding"]["profiled_launch_ms"] = round(rec["duration_ns"] / 1e6, 3)
-        alg_gbs = logical / avg_launch_s / 1e9
-        roof.update({
-                "algorithmic": {"bytes_per_launch": int(logical),
-                                "bytes_per_ray": round(logical / max(1.0, per_launch["rays"]), 1),
-                                "gbs": round(alg_gbs, 1),
-                                "note": "SURVEY §8(d) logical bytes (node/instance/primitive/shading records) "
-                                        "over the launch time; served from LDS (small scenes) or L2, not HBM"
-                                        + (f": {alg_gbs / 1e3:.1f} TB/s exceeds the 8 TB/s HBM peak, so HBM is not "
-                                           "this kernel's roof" if alg_gbs > HBM_PEAK_GBS else "")},
-                # traversal work per closest-hit query, from the counting pass
-                "per_ray": {k: round(per_launch[k] / max(1.0, per_launch["rays"]), 3)
-                            for k in ("nodes", "instances", "prims", "shades", "light_queries")}})
+        # the roofline (--full): traversal work from the counting pass, priced with the committed
+        # PMC record of this kernel, workload and build
+        roof = None
+        if args.full:
+            per_launch = {k: v / max(1, full["launches"]) for k, v in full.items()}  # one step's launches
+            logical = algorithmic_bytes(per_launch, shade_record_bytes(scene),
+                                        any(len(s.quads) for s in scene.shapes), traversal == "wide")
+            sys.path.insert(0, str(ROOT / "scripts"))
+            from roofline import VMEM_MIX_PEAK_GIPS
+            # the source hash the Makefile embedded in the library that ran (jt_version), not a hash of
+            # this tree: no compiler is invoked at run time (under a PMC profiler a child process that
+            # execs would be refused), and a record can only match the binary it describes
+            build = library_build_hash(lib)
+            rec, rec_src = roofline_record(workload, kernel, build)
+            # The roof that binds, from the PMC counts of this kernel on this workload and build
+            # (committed record) over THIS run's launch time (HIP events):
+            #  - LDS mode (small scenes: the scene is in LDS): VALU issue of partly idle waves —
+            #    achieved = useful FP32 lane-operations per second, peak = the CUs' FP32 lane rate;
+            #  - HBM mode (node / primitive records L2-resident): the vector-memory return path (TD) —
+            #    achieved = vector-memory read wave-instructions per second, peak = the measured
+            #    gather ceiling for the traversal's own node records (scripts/td_mix_bench.hip,
+            #    profiles/r04_tdmix/: 64-B wide records 40.6, 16-B binary rows 34.7 G wave-instr/s);
+            #    td_unstalled_frac (TD busy and not waiting on the cache) beside it agrees with frac.
+            # HBM itself (measured traffic / 8 TB/s) is reported beside it as hbm_frac.
+            lds_mode = "mode=lds" in desc
+            roof = {"bound": "valu" if lds_mode else "vmem/TD", "achieved": None, "peak": None,
+                    "unit": "G lane-ops/s" if lds_mode else "G wave-instr/s", "frac": None, "traffic": None,
+                    "hbm_achieved_gbs": None, "hbm_peak_gbs": HBM_PEAK_GBS, "hbm_frac": None,
+                    "source": rec_src, "build": build, "kernel": kernel, "launch": desc,
+                    "avg_launch_ms": round(avg_launch_s * 1e3, 3), "binding": None}
+            if rec:
+                d = rec["derived"]
+                if lds_mode and "valu_lane_ops" in d:
+                    achieved, peak = d["valu_lane_ops"] / avg_launch_s / 1e9, d["valu_peak_gops"]
+                elif not lds_mode and "vmem_rd_per_launch" in d:
+                    achieved, peak = d["vmem_rd_per_launch"] / avg_launch_s / 1e9, VMEM_MIX_PEAK_GIPS[traversal]
+                else:
+                    achieved = peak = None
+                if achieved is not None:
+                    roof.update(achieved=round(achieved, 2), peak=round(peak, 2), frac=round(achieved / peak, 5))
+                traffic = d["traffic_bytes"]  # measured HBM bytes per launch (PMC, gfx950-corrected)
+                roof.update(traffic=int(traffic), hbm_achieved_gbs=round(traffic / avg_launch_s / 1e9, 1),
+                            hbm_frac=round(traffic / avg_launch_s / 1e9 / HBM_PEAK_GBS, 5))
+                roof["binding"] = {k: d[k] for k in ("valu_issue_frac", "lane_util", "fp32_lane_frac", "td_busy_frac",
+                                                     "td_unstalled_frac", "td_tc_stall_frac_of_busy", "l2_hit_rate", "l1_hit_rate",
+                                                     "l1_accesses_per_vmem_rd", "l1_misses_per_vmem_rd",
+                                                     "vmem_mix_frac", "vmem_mix_frac_resident", "clock_ghz") if k in d}
+                roof["binding"]["write_bytes_per_launch"] = int(d["write_bytes"])
+                roof["binding"]["profiled_launch_ms"] = round(rec["duration_ns"] / 1e6, 3)
+            alg_gbs = logical / avg_launch_s / 1e9
+            roof.update({
+                    "algorithmic": {"bytes_per_launch": int(logical),
+                                    "bytes_per_ray": round(logical / max(1.0, per_launch["rays"]), 1),
+                                    "gbs": round(alg_gbs, 1),
+                                    "note": "SURVEY §8(d) logical bytes (node/instance/primitive/shading records) "
+                                            "over the launch time; served from LDS (small scenes) or L2, not HBM"
+                                            + (f": {alg_gbs / 1e3:.1f} TB/s exceeds the 8 TB/s HBM peak, so HBM is not "
+                                               "this kernel's roof" if alg_gbs > HBM_PEAK_GBS else "")},
+                    # traversal work per closest-hit query, from the counting pass
+                    "per_ray": {k: round(per_launch[k] / max(1.0, per_launch["rays"]), 3)
+                                for k in ("nodes", "instances", "prims", "shades", "light_queries")}})
         line = {
             "metric": metric_name(name, args.sampler, W, H, S) + (" (--highqualitybvh)" if args.highqualitybvh else ""),
             "value": round(value, 2), "unit": "Mrays/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "full": args.full,
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32",
             "data": f"scene: the reference's own {name} (assets/scenes/{name}), seed 0x5EED"
                     + (f"; {'; '.join(scene.notes)}" if scene.notes else ""),

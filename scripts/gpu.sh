@@ -82,11 +82,11 @@ for task in "$@"; do
         smoke)
             $S 300 "$O/smoke.log" python -c "import __graft_entry__ as g; g.smoke()" || exit 1 ;;
         bench)
-            $S 600 "$O/bench_$name.log" python bench.py $(wargs "$w") $(steps "$w") $extra || exit 1 ;;
+            $S 600 "$O/bench_$name.log" python bench.py --full $(wargs "$w") $(steps "$w") $extra || exit 1 ;;
         quick)
-            $S 400 "$O/quick_$name.log" python bench.py --no-cpu-baseline --no-reference-order $(wargs "$w") $(steps "$w") $extra || exit 1 ;;
+            $S 400 "$O/quick_$name.log" python bench.py --full --no-cpu-baseline --no-reference-order $(wargs "$w") $(steps "$w") $extra || exit 1 ;;
         sig)
-            $S 400 "$O/sig_$name.log" python bench.py --no-cpu-baseline --no-reference-order --write-signature $(wargs "$w") --steps 1 --warmup 0 || exit 1
+            $S 400 "$O/sig_$name.log" python bench.py --full --no-cpu-baseline --no-reference-order --write-signature $(wargs "$w") --steps 1 --warmup 0 || exit 1
             cp profiles/image_signatures.json "$O/image_signatures.json" ;;
         measure)
             wl=$(python bench.py --print-workload $(wargs "$w") $extra) || exit 1
@@ -95,12 +95,12 @@ for task in "$@"; do
             for rep in 1 2; do
                 for lib in $(echo "$extra" | tr ',' ' '); do
                     if [ "$lib" = base ]; then L=julia-raytracer_amd/build/libjtrace_hip.so; else L=julia-raytracer_amd/build/libjtrace_hip_$lib.so; fi
-                    JTRACE_LIB=$L $S 400 "$O/ab_${name}_${lib}_$rep.log" python bench.py --no-cpu-baseline --no-reference-order $(wargs "$w") $(steps "$w") || exit 1
+                    JTRACE_LIB=$L $S 400 "$O/ab_${name}_${lib}_$rep.log" python bench.py --full --no-cpu-baseline --no-reference-order $(wargs "$w") $(steps "$w") || exit 1
                     echo "$w $lib rep$rep => $(grep -h '"value"' "$O/ab_${name}_${lib}_$rep.log" | python -c 'import sys,json; d=json.loads(sys.stdin.read()); print(round(d["value"],1))')" | tee -a "$O/ab_summary.txt"
                 done
             done ;;
         prof)
-            $S 300 "$O/prof_$name.log" rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_$name" -o kt -- python3 bench.py --no-cpu-baseline --no-reference-order $(wargs "$w") --steps 2 --warmup 1 || exit 1 ;;
+            $S 300 "$O/prof_$name.log" rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_$name" -o kt -- python3 bench.py --full --no-cpu-baseline --no-reference-order $(wargs "$w") --steps 2 --warmup 1 || exit 1 ;;
         stamps)
             $S 400 "$O/stamps_$name.log" python scripts/stamps.py $(wargs "$w") || exit 1 ;;
         tdmix)
@@ -108,7 +108,7 @@ for task in "$@"; do
             $S 200 "$O/tdmix_rates$name.log" timeout -k 10 180 $TD $w $extra || exit 1
             $S 200 "$O/tdmix_pmc$name.log" timeout -s KILL 180 rocprofv3 --pmc TD_TD_BUSY_sum TCC_HIT_sum TCC_MISS_sum GRBM_GUI_ACTIVE --output-format csv -d "$O/tdmix_pmc$name" -o pmc -- $TD $w $extra || exit 1 ;;
         rehearse)
-            JT_BENCH_BACKEND=gloo JT_BENCH_DEVICE=0 $S 300 "$O/rehearsal_n${w}_gloo_one_gpu.log" python -m torch.distributed.run --nnodes=1 --nproc-per-node "$w" --master-addr 127.0.0.1 --master-port $((29500 + w)) bench.py --gpus "$w" --steps 3 --warmup 1 --no-cpu-baseline || exit 1 ;;
+            JT_BENCH_BACKEND=gloo JT_BENCH_DEVICE=0 $S 300 "$O/rehearsal_n${w}_gloo_one_gpu.log" python -m torch.distributed.run --nnodes=1 --nproc-per-node "$w" --master-addr 127.0.0.1 --master-port $((29500 + w)) bench.py --gpus "$w" --steps 3 --warmup 1 --full --no-cpu-baseline || exit 1 ;;
         host)
             { nproc; lscpu | grep -E "Model name|Socket|Core|Thread"; rocm-smi --showproductname 2>/dev/null | head -20; } > "$O/host.txt" 2>&1 ;;
         *) echo "unknown task $task" >&2; exit 2 ;;
