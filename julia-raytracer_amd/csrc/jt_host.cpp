@@ -227,7 +227,8 @@ static int export_tree(Builder& b, jt_bvh_tree* out) {
     out->primitives = (int32_t*)std::malloc(sizeof(int32_t) * std::max<size_t>(1, b.prims.size()));
     if (!out->nodes || !out->primitives) return JT_ERR_NOMEM;
     std::memcpy(out->nodes, b.nodes.data(), sizeof(jt_bvh_node) * b.nodes.size());
-    std::memcpy(out->primitives, b.prims.data(), sizeof(int32_t) * b.prims.size());
+    if (!b.prims.empty())  // an empty tree (no instances): data() may be NULL, which memcpy must not get
+        std::memcpy(out->primitives, b.prims.data(), sizeof(int32_t) * b.prims.size());
     return JT_OK;
 }
 

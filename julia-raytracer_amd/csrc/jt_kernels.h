@@ -17,7 +17,8 @@
 //
 // Build: every kernel configuration (JT_LAUNCH_CONFIG) is instantiated in its own translation
 // unit (jt_kv.hip, compiled once per configuration) so the kernels compile in parallel; the host
-// context (jt_trace.hip) only declares them.
+// context (jt_trace.hip) only declares them. The records the kernels read are declared in
+// jt_records.h (through jt_device.h) and written on the host by jt_layout.cpp.
 #pragma once
 
 #include <hip/hip_runtime.h>

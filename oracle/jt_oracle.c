@@ -510,7 +510,7 @@ static scene_isec intersect_instance_bvh(const ctx_t* c, int inst_id, ray3 ray, 
 
 /* ------------------------------------------------- wide traversal (JT_TRAVERSAL_WIDE) */
 /* The build's 4-wide traversal (include/jtrace.h JT_TRAVERSAL_WIDE), restated from
- * its specification independently of the product's builder (jt_trace.hip build_wide): a record
+ * its specification independently of the product's builder (jt_layout.cpp build_wide): a record
  * per internal binary node N (or the root leaf) holding N's grandchildren in slots [LL, LR, RL,
  * RR] (a leaf child alone in its pair's first slot), their boxes quantised to bytes relative to
  * N's box, visited near child first in the binary DFS order; every record's children are tested
