@@ -65,7 +65,11 @@ __device__ __forceinline__ float length(v3 a) { return __builtin_sqrtf(dot(a, a)
 // instruction; the compare-and-select form otherwise). A NaN result may carry another payload than
 // Julia's (x's or y's): no decision and no stored value depends on a NaN's payload.
 #ifndef JT_NAN_PROP
+#if defined(__gfx950__)
 #define JT_NAN_PROP 1
+#else
+#define JT_NAN_PROP 0  // other targets (ARCH=gfx942) and the host pass: compare and select
+#endif
 #endif
 __device__ __forceinline__ float jl_min3(float a, float b, float c) {
     float r;

@@ -27,6 +27,7 @@
 
 #include "jt_bsdf.h"
 #include "jt_device.h"
+#include "jt_push.h"
 
 #ifndef JT_STAMPS
 #define JT_STAMPS 0
@@ -666,6 +667,19 @@ __device__ __forceinline__ void node_step(const DScene& S, Trav& T, int* stack, 
     const unsigned meta = __float_as_uint(nb.w);
     const int start = __float_as_int(nb.z);
     const int num = (int)(meta & 0xffffu);
+    if (!OVF && !(JT_CHILD_PRETEST && NCACHE)) {
+        // fixed stack, no pre-test: the entries of either arm are affine in the slot number
+        // (jt_push.h), so every lane writes PUSH_SLOTS entries straight-line — the surplus ones
+        // repeat the top entry, or land in the slot just popped — instead of a divergent branch
+        // per arm and a loop per TLAS-leaf instance. The leaf cursor is set by selects.
+        const PushPlan p = push_plan(meta, start, type, blas, T.negmask, T.sp);
+#pragma unroll
+        for (int j = 0; j < PUSH_SLOTS; j++) stack[p.slot[j] * BLOCK] = (int)p.value[j];
+        T.sp += p.npush;
+        T.prim = p.leaf ? start : T.prim;
+        T.nprim = p.leaf ? num : T.nprim;
+        return;
+    }
     if (meta >> 24) {  // internal: for d[axis] >= 0 push start, start+1 (start+1 pops first)
         const int axis = (int)((meta >> 16) & 0xffu);
         // d[axis] < 0, or (JT_TRAVERSAL_NEAR) d[axis] >= 0: start+1 is pushed first, start pops first
@@ -1097,17 +1111,82 @@ __device__ __forceinline__ bool light_hit(const DScene& S, const DParams& P, Pat
 // here, where most of the wave's lanes run their chains side by side, instead of one-prim-step
 // queries and light-hit steps of a few lanes inside the traversal phase. Returns light_hit's
 // "path done"; otherwise st.phase is PH_SCENE (the next bounce's scene query).
+#ifndef JT_LIGHT_LEAF_STEP
+#define JT_LIGHT_LEAF_STEP 1  // 0: every inline light query goes through query_start + node_step (A/B runs)
+#endif
+// One query of an inline chain in the binary fixed-stack LDS kernels: intersect_instance_bvh of an
+// instance whose BLAS is one leaf (INST_LEAF_ROOT), without the stack round trip of query_start +
+// node_step — the instance record and its root node are read directly, the root box is tested by
+// the same intersect_bbox, and the leaf cursor is set by selects. dinv and negmask are those of
+// query_begin for direction d: the direction is the same for every query of a bounce's chain, so
+// the caller computes them once. The query's state ends as query_start + node_step leave it
+// (sp 0; prim 0 when the box fails), and one instance and one node are counted.
+template <int COUNT, int F>
+__device__ __forceinline__ void inst_leaf_query(const DScene& S, Trav& T, v3 o, v3 d, v3 dinv, int negmask, int inst,
+                                                Counters& cnt) {
+    constexpr bool XF = (F & FT_XFORM) != 0;
+    T.wo = o;
+    T.wd = d;
+    T.wdinv = dinv;
+    T.lo = o;
+    T.ld = d;
+    T.ldinv = dinv;
+    T.tmax = __builtin_inff();
+    T.nh = 0;
+    T.h_inst = -1;
+    T.h_elem = -1;
+    T.h_u = 0;
+    T.h_v = 0;
+    T.inst_space = 0;
+    T.negmask = negmask;
+    T.sp = 0;
+    T.low = 0;
+    T.nxt = W_EMPTY;
+    if (COUNT) cnt.instances++;
+    const int4 ib = S.inst_blas[inst];
+    if (XF && !ib.y) {
+        const DInstTrav it = S.inst_trav[inst];
+        const fr3 inv = frame_from(it.i0, it.i1, it.i2);
+        T.lo = transform_point(inv, T.wo);
+        T.ld = transform_vector(inv, T.wd);
+        T.ldinv = V3(jl_rcp(T.ld.x), jl_rcp(T.ld.y), jl_rcp(T.ld.z));
+        T.negmask = neg_mask(T.ld, query_flip(S, T));
+        T.inst_space = 1;
+    }
+    T.cur_inst = inst;
+    T.cur_kind = ib.z;
+    if (COUNT) cnt.nodes++;
+    const DNode nd = S.nodes[ib.x];
+    const bool pass = intersect_bbox(T.lo, T.ldinv, ray_eps, T.tmax, nd.a, nd.b);
+    T.prim = pass ? __float_as_int(nd.b.z) : 0;
+    T.nprim = pass ? (int)(__float_as_uint(nd.b.w) & 0xffffu) : 0;
+}
+
 template <bool WIDE, int RING, bool OVF, int COUNT, bool NCACHE, int F, class CountLq>
 __device__ __forceinline__ bool light_chain(const DScene& S, const DParams& P, Path& st, Trav& T, int* stack, int pixel,
                                             Counters& cnt, CountLq count_lq) {
+    // No tie re-run is needed here: a one-leaf BLAS has no child order (INST_LEAF_ROOT). The
+    // FT_MESH kernel (bathroom1) keeps the re-run loop anyway, never taken: its compiled
+    // layout is 4 % faster with it, features2's kernel 1.5 % slower (gpurun_out/r05v)
+    constexpr bool RERUN_LOOP = (F & ~FT_LINL) == (FT_TEX | FT_ATTR | FT_MAT | FT_OPAC | FT_XFORM);  // FT_MESH
+    if (JT_LIGHT_LEAF_STEP && !WIDE && !OVF && !NCACHE && !RERUN_LOOP) {
+        // st.d does not change while the chain runs (light_hit moves st.o only): 1/d and the push
+        // mask of every query of the chain are computed once
+        do {
+            count_lq();
+            const v3 d = st.d;
+            const v3 dinv = V3(jl_rcp(d.x), jl_rcp(d.y), jl_rcp(d.z));  // ray_dinv (src/bvh.jl:322), no guard
+            const int negmask = neg_mask(d, S.order_flip);
+            inst_leaf_query<COUNT, F>(S, T, st.o, d, dinv, negmask, S.lights[st.li].instance, cnt);
+            while (T.nprim > 0) prim_step<COUNT, F>(S, T, cnt);
+            if (light_hit<F>(S, P, st, query_hit(T))) return true;
+        } while (st.phase == PH_LIGHT);
+        return false;
+    }
     do {
         count_lq();
         const int inst = S.lights[st.li].instance;
         query_start<WIDE>(S, T, st.o, st.d, inst, stack);
-        // No tie re-run is needed here: a one-leaf BLAS has no child order (INST_LEAF_ROOT). The
-        // FT_MESH kernel (bathroom1) keeps the re-run loop anyway, never taken: its compiled
-        // layout is 4 % faster with it, features2's kernel 1.5 % slower (gpurun_out/r05v)
-        constexpr bool RERUN_LOOP = (F & ~FT_LINL) == (FT_TEX | FT_ATTR | FT_MAT | FT_OPAC | FT_XFORM);  // FT_MESH
         do {
             node_step_any<WIDE, RING, OVF, COUNT, NCACHE, F>(S, T, stack, pixel, cnt);  // instance + its one-leaf root
             while (T.nprim > 0) prim_step<COUNT, F>(S, T, cnt);
@@ -1570,7 +1649,13 @@ __device__ __forceinline__ int item_pixel(unsigned item, const DParams& P, int t
 // spills from 1-2 to 4-6 VGPRs)
 __host__ __device__ __forceinline__ int item_slot(unsigned item, const DParams& P) {
     const int t = (int)(item >> 6);
-    const int u = (int)((float)(t - P.tile_offset) * (1.0f / (float)P.tile_stride) + 0.5f);
+    float inv = 1.0f / (float)P.tile_stride;
+#if defined(__HIP_DEVICE_COMPILE__)
+    // wave-uniform and loop-invariant: hoisted out of the persistent loop it held a VGPR for the
+    // whole kernel (the one the 96-VGPR cornellbox kernel spilled); as a scalar it costs none
+    inv = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(inv)));
+#endif
+    const int u = (int)((float)(t - P.tile_offset) * inv + 0.5f);
     return u * 64 + (int)(item & 63u);
 }
 // running-mean weight of global sample s within its stream
