@@ -16,6 +16,8 @@
  *   jt_trace_range     == trace_samples over an explicit global sample range (multi-GPU shards)
  *   jt_get_image       == get_image (src/trace.jl:676) — the running-mean RGBA buffer
  *   jt_get_aovs        == TraceState.albedo / normal / hits (src/trace.jl:87-100)
+ *   jt_denoise         (the build's own: the reference's --denoise is forced off, src/jtrace.jl:35-46)
+ *                      an a-trous filter over those means; jt_get_denoised reads its result
  *   jt_destroy / jt_last_error — lifetime and error reporting (the reference throws Julia exceptions)
  *
  * Host helpers (run on the CPU, no device needed) that restate the reference's host code
@@ -260,6 +262,15 @@ typedef struct jt_device_buffers {
     void* stream;  /* hipStream_t the context launches on */
 } jt_device_buffers;
 
+/* Parameters of the denoiser (jt_denoise). iterations: 1..8; the sigmas and the floor finite, > 0. */
+typedef struct jt_denoise_params {
+    int32_t iterations;  /* a-trous iterations I; iteration i taps at a distance of 2^i pixels */
+    float sigma_color;   /* of the demodulated radiance at iteration 0; halved every iteration */
+    float sigma_normal;
+    float sigma_albedo;
+    float albedo_floor;  /* lower bound of the albedo the radiance is divided by */
+} jt_denoise_params;
+
 typedef struct jt_ctx jt_ctx;
 
 /* ---- library ---------------------------------------------------------------------- */
@@ -368,6 +379,45 @@ int jt_get_size(const jt_ctx* ctx, int32_t* width, int32_t* height);
 int jt_get_image(jt_ctx* ctx, float* rgba);                          /* W*H*4 */
 int jt_get_aovs(jt_ctx* ctx, float* albedo, float* normal, int64_t* hits); /* W*H*3, W*H*3, W*H */
 int jt_get_counters(jt_ctx* ctx, jt_counters* out);
+
+/* ---- denoiser ------------------------------------------------------------------------ */
+/* The edge-avoiding a-trous wavelet filter of Dammertz et al. (HPG 2010) on albedo-demodulated
+ * radiance, guided by the albedo and normal means (the reference mirrors a --denoise flag and
+ * switches it off, src/jtrace.jl; this is the build's own). All float32, no FMA. With c the
+ * mean radiance RGBA, a the mean albedo, n the mean normal (as accumulated, not renormalised):
+ *   m = max(a, albedo_floor) per channel;  d_0 = c.rgb / m;
+ *   for i = 0 .. iterations-1, s = 2^i, sc_i = sigma_color / s, at every pixel p:
+ *     d_{i+1}(p) = sum_q w(p,q) d_i(q) / sum_q w(p,q),  q = p + s (dx, dy), dx, dy in -2..2,
+ *     taps outside the image skipped;
+ *     w(p,q) = k[dy+2] k[dx+2] exp(-(|d_i(p)-d_i(q)|^2 / sc_i^2 + |n(p)-n(q)|^2 / sigma_normal^2
+ *                                    + |a(p)-a(q)|^2 / sigma_albedo^2)),
+ *     k = {1/16, 1/4, 3/8, 1/4, 1/16}, |.|^2 summed over the three channels (the centre tap
+ *     weighs 9/64, so the denominator is never 0);
+ *   out.rgb = d_I * m;  out.a = c.a.
+ * jt_denoise_defaults (host only): iterations 5, sigma_color 8 / sqrtf(max(samples, 1)) (the
+ * noise falls as 1 / sqrt(spp)), sigma_normal 0.3, sigma_albedo 0.1, albedo_floor 0.01. */
+int jt_denoise_defaults(int32_t samples, jt_denoise_params* out);
+/* Filters the context's running means into a buffer the context owns (allocated with its
+ * scratch by the first call, kept across jt_reset, freed by jt_destroy). params NULL: the
+ * defaults for the samples traced so far. Traces the queued samples first, as every reader
+ * does; image, albedo, normal, hits and every jt_counters field stay bit for bit as they were.
+ * JT_ERR_STATE when no sample has been traced or the context has failed; JT_ERR_INVALID
+ * (naming the field) for iterations outside 1..8 or a sigma or floor that is not finite and
+ * > 0. A multi-device context reduces image, albedo and normal as jt_get_image / jt_get_aovs do
+ * and filters them on its first device. */
+int jt_denoise(jt_ctx* ctx, const jt_denoise_params* params);
+/* The result of the last jt_denoise, W*H*4. JT_ERR_STATE when none has run since the last
+ * sample was traced (or queued) or since jt_reset: a stale result is never returned. */
+int jt_get_denoised(jt_ctx* ctx, float* rgba);
+/* The same filter on the caller's host arrays (rgba W*H*4, albedo W*H*3, normal W*H*3, row-major)
+ * on HIP device `device`, into out_rgba (W*H*4): for callers who reduce the shards of a render
+ * themselves (one process per GPU). Arguments are checked before any device work; params is
+ * required; width, height >= 1 and within jt_create's image size limit. Non-finite pixels in
+ * the arrays are the caller's responsibility (they spread to every pixel whose taps reach them);
+ * the tracer's own buffers never hold any. */
+int jt_denoise_image(const float* rgba, const float* albedo, const float* normal, int32_t width, int32_t height,
+                     const jt_denoise_params* params, int32_t device, float* out_rgba);
+
 /* zero accumulators (at once if their device pointers were handed out, else before they are
  * next read or overwritten), samples = 0, queued samples dropped */
 int jt_reset(jt_ctx* ctx);

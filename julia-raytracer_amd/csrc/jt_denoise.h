@@ -1,0 +1,21 @@
+// jt_denoise.h — the denoiser's entry points for the device context (jt_trace.hip); the filter,
+// its kernels and jt_denoise_image are in jt_denoise.hip. Not part of the ABI.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include "jt_internal.h"
+
+namespace jt {
+
+// JT_ERR_INVALID naming the field, before any device work
+int denoise_check_params(const jt_denoise_params* p);
+int denoise_check_size(int32_t width, int32_t height);
+
+// The filter of include/jtrace.h (jt_denoise) over device arrays of width * height float4:
+// image RGBA, albedo and normal xyz (w ignored), two scratch buffers and the result. Every
+// launch goes on `stream`, nothing waits: the caller synchronises. out may not alias an input.
+hipError_t denoise_launch(hipStream_t stream, const float4* image, const float4* albedo, const float4* normal, int width,
+                          int height, const jt_denoise_params& p, float4* ping, float4* pong, float4* out);
+
+}  // namespace jt

@@ -14,6 +14,7 @@
 #include <string>
 #include <vector>
 
+#include "jt_denoise.h"
 #include "jt_internal.h"
 #include "jt_kernels.h"
 #include "jt_layout.h"
@@ -129,6 +130,12 @@ struct jt_ctx {
     bool tile_split = false;
     float* red = nullptr;         // device 0: reduce target, W*H float4
     long long* red_hits = nullptr;
+    // the denoiser (jt_denoise, jt_denoise.hip): two scratch buffers and the result, float4[W*H]
+    // each, allocated by the first jt_denoise and kept across jt_reset. A multi-device context
+    // filters the reduced host arrays on device 0 and keeps the result on the host instead
+    float4* dn[3] = {nullptr, nullptr, nullptr};
+    std::vector<float> dn_host;
+    bool denoised = false;  // the result is the filter of the current running means
 };
 
 namespace jtk {
@@ -791,6 +798,7 @@ int finish_aovs(jt_ctx* c) {
 
 int jt_reset(jt_ctx* c) {
     if (!c) return jt::fail(JT_ERR_INVALID, "ctx is NULL");
+    c->denoised = false;
     if (!c->sub.empty()) {
         for (jt_ctx* s : c->sub) {
             const int st = jt_reset(s);
@@ -1086,6 +1094,7 @@ int jt_trace_range(jt_ctx* c, int32_t s0, int32_t s1) {
     if (c->first >= 0 && s0 != c->next)
         return jt::fail(JT_ERR_STATE, "samples must be accumulated in order (expected " + std::to_string(c->next) + ")");
     if (c->first < 0) c->first = s0;
+    c->denoised = false;  // jt_get_denoised never returns the filter of fewer samples
     // queue the range behind the deferred ones (jt_ctx::pend0); trace them all once enough are
     // queued, the render is complete (params.samples: the end of Jtrace.main's loop), or a caller
     // reads the accumulators in place (jt_get_device_buffers: it sees every range at once)
@@ -1189,6 +1198,59 @@ int jt_get_aovs(jt_ctx* c, float* albedo, float* normal, int64_t* hits) {
         }
     }
     return JT_OK;
+}
+
+int jt_denoise(jt_ctx* c, const jt_denoise_params* params) {
+    if (!c) return jt::fail(JT_ERR_INVALID, "ctx is NULL");
+    jt_denoise_params p{};
+    if (params) {
+        if (const int st = jt::denoise_check_params(params)) return st;
+        p = *params;
+    }
+    if (c->failed) return jt::fail(JT_ERR_STATE, "a previous launch failed; jt_reset the context");
+    if (const int st = flush(c)) return st;
+    const int samples = c->first < 0 ? 0 : c->next - c->first;
+    if (samples < 1) return jt::fail(JT_ERR_STATE, "no sample has been traced");
+    if (!params) (void)jt_denoise_defaults(samples, &p);
+    c->denoised = false;
+    const size_t np = (size_t)c->width * c->height;
+    if (!c->sub.empty()) {
+        // the devices' means reduced as jt_get_image / jt_get_aovs do, filtered on device 0
+        std::vector<float> img(np * 4), alb(np * 3), nrm(np * 3);
+        int st;
+        if ((st = jt_get_image(c, img.data())) || (st = jt_get_aovs(c, alb.data(), nrm.data(), nullptr))) return st;
+        c->dn_host.resize(np * 4);
+        if ((st = jt_denoise_image(img.data(), alb.data(), nrm.data(), c->width, c->height, &p, c->sub[0]->device,
+                                   c->dn_host.data())))
+            return st;
+        c->denoised = true;
+        return JT_OK;
+    }
+    int st;
+    if ((st = zero_if_stale(c)) || (st = finish_aovs(c))) return st;
+    (void)hipSetDevice(c->device);
+    for (int k = 0; k < 3; k++)
+        if (!c->dn[k] && (st = device_alloc(c, np * 16, "denoise buffers", (void**)&c->dn[k]))) return st;
+    // neither counted in jt_counters (launches, kernel_ms) nor touching an accumulator
+    hipError_t e = jt::denoise_launch(c->stream, c->A.image, c->A.albedo, c->A.normal, c->width, c->height, p, c->dn[0],
+                                      c->dn[1], c->dn[2]);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return hip_fail(e, "denoise");
+    c->denoised = true;
+    return JT_OK;
+}
+
+int jt_get_denoised(jt_ctx* c, float* rgba) {
+    if (!c || !rgba) return jt::fail(JT_ERR_INVALID, "NULL argument");
+    if (!c->denoised) return jt::fail(JT_ERR_STATE, "no jt_denoise since the last sample was traced or jt_reset");
+    const size_t np = (size_t)c->width * c->height;
+    if (!c->sub.empty()) {
+        std::memcpy(rgba, c->dn_host.data(), np * 16);
+        return JT_OK;
+    }
+    (void)hipSetDevice(c->device);
+    hipError_t e = hipMemcpy(rgba, c->dn[2], np * 16, hipMemcpyDeviceToHost);
+    return e == hipSuccess ? JT_OK : hip_fail(e, "hipMemcpy denoised");
 }
 
 int jt_get_counters(jt_ctx* c, jt_counters* out) {

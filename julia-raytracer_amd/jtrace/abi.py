@@ -132,6 +132,14 @@ class jt_device_buffers(C.Structure):
                 ("stream", C.c_void_p)]
 
 
+class jt_denoise_params(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_albedo", C.c_float), ("albedo_floor", C.c_float)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 assert C.sizeof(jt_bvh_node) == 32
 
 
@@ -274,6 +282,11 @@ def _declare(lib):
     lib.jt_get_image.argtypes = [C.c_void_p, f32p]
     lib.jt_get_aovs.argtypes = [C.c_void_p, f32p, f32p, C.POINTER(C.c_int64)]
     lib.jt_get_counters.argtypes = [C.c_void_p, C.POINTER(jt_counters)]
+    lib.jt_denoise_defaults.argtypes = [C.c_int32, C.POINTER(jt_denoise_params)]
+    lib.jt_denoise.argtypes = [C.c_void_p, C.POINTER(jt_denoise_params)]
+    lib.jt_get_denoised.argtypes = [C.c_void_p, f32p]
+    lib.jt_denoise_image.argtypes = [f32p, f32p, f32p, C.c_int32, C.c_int32, C.POINTER(jt_denoise_params),
+                                     C.c_int32, f32p]
     lib.jt_reset.argtypes = [C.c_void_p]
     lib.jt_get_device_buffers.argtypes = [C.c_void_p, C.POINTER(jt_device_buffers)]
     lib.jt_set_counters.argtypes = [C.c_void_p, C.c_int32]
@@ -290,7 +303,7 @@ EXPORTED_SYMBOLS = [
     "jt_free_scene_bvh", "jt_make_lights", "jt_free_lights", "jt_image_size", "jt_create", "jt_create_multi",
     "jt_trace_samples", "jt_trace_range", "jt_get_streams", "jt_get_samples", "jt_get_size", "jt_get_image",
     "jt_get_aovs", "jt_get_counters", "jt_reset", "jt_get_device_buffers", "jt_set_counters", "jt_describe", "jt_synchronize",
-    "jt_destroy",
+    "jt_destroy", "jt_denoise_defaults", "jt_denoise", "jt_get_denoised", "jt_denoise_image",
 ]
 
 

@@ -39,9 +39,6 @@ def run(params: Params, out=print) -> dict:
     if params.envname != "":
         out("envname is not yet supported")
         params.envname = ""
-    if params.denoise:
-        out("denoise is not yet supported")
-        params.denoise = False
     render_start = time.perf_counter()
     out(f"loading scene {params.scene}...")
     t0 = time.perf_counter()
@@ -73,14 +70,23 @@ def run(params: Params, out=print) -> dict:
             f"ETC: {format_seconds(etc)}")
     render_s = time.perf_counter() - sampling_start
     out(f"rendered in {format_seconds(render_s)} ({render_s:.3f}s)")
+    if params.denoise:  # the a-trous filter over the albedo and normal means (jt_denoise)
+        out("denoising...")
+        t0 = time.perf_counter()
+        image = state.denoise()
+        out(f"denoised in {format_seconds(time.perf_counter() - t0)}")
     out("saving image...")
-    image = state.get_image()
+    if not params.denoise:
+        image = state.get_image()
     save_image(params.output, image, state.width, state.height)
     out(f"saved image to {params.output}")
     out(f"total time: {format_seconds(time.perf_counter() - render_start)}")
     counters = state.counters()
     state.close()
-    return {"render_s": render_s, "width": state.width, "height": state.height, "counters": counters}
+    result = {"render_s": render_s, "width": state.width, "height": state.height, "counters": counters}
+    if params.denoise:
+        result["denoised"] = True
+    return result
 
 
 def main(args=None):

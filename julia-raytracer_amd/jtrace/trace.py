@@ -5,6 +5,8 @@
     TraceState / make_trace_state   src/trace.jl:87,189 -> jt_create (device context)
     trace_samples(state)            src/trace.jl:215   -> jt_trace_samples (one batch)
     get_image(state)                src/trace.jl:676   -> jt_get_image
+    state.denoise() / denoise_image / denoise_defaults (the build's own) -> jt_denoise, jt_get_denoised,
+                                                       jt_denoise_image, jt_denoise_defaults
 
 There is no CPU fallback anywhere in this module: every call goes through libjtrace_hip.so.
 """
@@ -144,6 +146,18 @@ class TraceState:
         del n
         return alb, nrm, hits
 
+    def denoise(self, params: abi.jt_denoise_params | None = None, **overrides) -> np.ndarray:
+        """jt_denoise then jt_get_denoised: the (H, W, 4) float32 a-trous filter of the running
+        means (include/jtrace.h). params None: the defaults for the samples traced so far;
+        overrides replace single fields (iterations, sigma_color, ...) of either."""
+        if overrides and params is None:
+            params = denoise_defaults(self.samples, self.lib)
+        params = _with_overrides(params, overrides)
+        abi.check(self.lib, self.lib.jt_denoise(self.handle, None if params is None else C.byref(params)))
+        out = np.empty((self.height, self.width, 4), np.float32)
+        abi.check(self.lib, self.lib.jt_get_denoised(self.handle, out.ctypes.data_as(abi.f32p)))
+        return out
+
     def counters(self) -> dict:
         c = abi.jt_counters()
         abi.check(self.lib, self.lib.jt_get_counters(self.handle, C.byref(c)))
@@ -197,3 +211,42 @@ def trace_samples(state: TraceState):
 
 def get_image(state: TraceState) -> np.ndarray:
     return state.get_image()
+
+
+def _with_overrides(params, overrides):
+    if not overrides:
+        return params
+    p = abi.jt_denoise_params.from_buffer_copy(params)
+    names = [name for name, _ in abi.jt_denoise_params._fields_]
+    for name, value in overrides.items():
+        if name not in names:
+            raise TypeError(f"unknown denoise parameter {name!r} (one of {', '.join(names)})")
+        setattr(p, name, value)
+    return p
+
+
+def denoise_defaults(samples: int, lib=None) -> abi.jt_denoise_params:
+    """jt_denoise_defaults: the denoiser's parameters for a render of `samples` samples per pixel."""
+    lib = lib or abi.load_library()
+    p = abi.jt_denoise_params()
+    abi.check(lib, lib.jt_denoise_defaults(int(samples), C.byref(p)))
+    return p
+
+
+def denoise_image(rgba, albedo, normal, device: int = 0, params: abi.jt_denoise_params | None = None, samples: int = 1,
+                  lib=None, **overrides) -> np.ndarray:
+    """jt_denoise_image: the denoiser on host arrays (H, W, 4), (H, W, 3), (H, W, 3) -> (H, W, 4)
+    float32, on HIP device `device`. params None: the defaults for `samples` samples per pixel;
+    overrides replace single fields."""
+    lib = lib or abi.load_library()
+    rgba = np.ascontiguousarray(rgba, np.float32)
+    albedo = np.ascontiguousarray(albedo, np.float32)
+    normal = np.ascontiguousarray(normal, np.float32)
+    if rgba.ndim != 3 or rgba.shape[2] != 4 or albedo.shape != rgba.shape[:2] + (3,) or normal.shape != albedo.shape:
+        raise ValueError(f"expected (H, W, 4), (H, W, 3), (H, W, 3) arrays, got {rgba.shape}, {albedo.shape}, {normal.shape}")
+    p = _with_overrides(params if params is not None else denoise_defaults(samples, lib), overrides)
+    out = np.empty_like(rgba)
+    abi.check(lib, lib.jt_denoise_image(rgba.ctypes.data_as(abi.f32p), albedo.ctypes.data_as(abi.f32p),
+                                        normal.ctypes.data_as(abi.f32p), rgba.shape[1], rgba.shape[0], C.byref(p),
+                                        int(device), out.ctypes.data_as(abi.f32p)))
+    return out
