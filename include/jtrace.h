@@ -18,6 +18,8 @@
  *   jt_get_aovs        == TraceState.albedo / normal / hits (src/trace.jl:87-100)
  *   jt_denoise         (the build's own: the reference's --denoise is forced off, src/jtrace.jl:35-46)
  *                      an a-trous filter over those means; jt_get_denoised reads its result
+ *   jt_get_variance    (the build's own) the per-pixel variance of the image, from the spread of
+ *                      the sample streams' means; jt_get_noise its image-level relative RMS error
  *   jt_destroy / jt_last_error — lifetime and error reporting (the reference throws Julia exceptions)
  *
  * Host helpers (run on the CPU, no device needed) that restate the reference's host code
@@ -417,6 +419,33 @@ int jt_get_denoised(jt_ctx* ctx, float* rgba);
  * the tracer's own buffers never hold any. */
 int jt_denoise_image(const float* rgba, const float* albedo, const float* normal, int32_t width, int32_t height,
                      const jt_denoise_params* params, int32_t device, float* out_rgba);
+
+/* ---- error estimate -------------------------------------------------------------------- */
+/* The per-pixel variance of the image, from the spread of the sample streams' means. A
+ * single-device context with k > 1 streams (jt_get_streams) keeps k independent running means
+ * per pixel; after n >= 2 local samples ns = min(n, k) of them hold a sample, stream j n_j
+ * (jt_trace_range states the rule). With m_j stream j's mean RGBA, w_j = (float)((double)n_j / n)
+ * the weight it was combined with, and mu the image pixel as jt_get_image returns it, per
+ * channel, float32, no FMA:
+ *   acc = 0;  for j = 0 .. ns-1 in order:  d = m_j - mu;  acc = acc + (d * d) * w_j
+ *   var = acc / (float)(ns - 1)
+ * the between-stream estimate of Var(mu), the variance OF THE MEAN (it falls as 1 / n).
+ * jt_get_variance copies var out, W*H*4; pixels a tile share (option tile_share) does not
+ * trace are 0. jt_get_noise is the image's relative RMS error over the N pixels the context
+ * traces: with V = sum_p ((var.x + var.y) + var.z) and M = sum_p ((mu.x + mu.y) + mu.z),
+ *   noise = sqrt(3 N V) / M  ( = sqrt(mean channel variance) / mean channel value ), 0 when M == 0,
+ * the sums per workgroup in float32 on the device (no atomics: deterministic), over the
+ * workgroups in double on the host.
+ * Both trace the queued samples first, as every reader does, and leave image, albedo, normal,
+ * hits, the stream means and every jt_counters field as a flush alone would; the estimate lives
+ * in buffers the context owns (allocated by the first call, kept across jt_reset, freed by
+ * jt_destroy), and a result computed for the current samples serves both calls.
+ * JT_ERR_INVALID (naming the argument) for a NULL ctx or output; JT_ERR_UNSUPPORTED for a
+ * multi-device context (jt_create_multi); JT_ERR_STATE when the context has failed, when no
+ * sample has been traced (also after jt_reset), or when fewer than two streams hold a sample:
+ * a one-stream context (batch 1 without the option streams) or n < 2. */
+int jt_get_variance(jt_ctx* ctx, float* var_rgba);   /* W*H*4, variance of the mean per channel */
+int jt_get_noise(jt_ctx* ctx, double* noise);
 
 /* zero accumulators (at once if their device pointers were handed out, else before they are
  * next read or overwritten), samples = 0, queued samples dropped */

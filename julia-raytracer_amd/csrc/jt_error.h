@@ -1,0 +1,35 @@
+// jt_error.h — the per-pixel error estimate's entry point for the device context (jt_trace.hip);
+// the kernel is in jt_error.hip. Not part of the ABI.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include "jt_records.h"
+
+namespace jt {
+
+constexpr int ERR_BLOCK = 256;  // threads per workgroup: four 8x8 tiles, as combine_kernel's
+
+// One launch over the slots of a context's stream means (DAccum::part_img, jt_kernels.h), with
+// combine_kernel's indexing: thread g is lane g & 63 of launch tile g >> 6, stream j's record of
+// its pixel is part_img[j * nslot + g].
+struct DError {
+    const float4* part_img;
+    const float4* image;      // the combined means, as combine_kernel wrote them
+    float4* var;              // float4[width * height]: the variance of the mean per channel
+    float2* block_sums;       // one (V, M) pair per workgroup
+    int nslot;
+    int width, height;
+    int tiles;                // launch tiles (launch_tiles)
+    int tile_stride, tile_offset;
+    int ns;                   // streams that hold a sample, >= 2
+    float w[JT_MAX_STREAMS];  // their weights n_j / n: the last launch's DCombine
+};
+
+// workgroups of the launch: every slot of the launch's tiles
+inline int error_blocks(int tiles) { return (int)(((long long)tiles * 64 + ERR_BLOCK - 1) / ERR_BLOCK); }
+
+// Enqueues the kernel on `stream`; nothing waits, the caller synchronises.
+hipError_t error_launch(hipStream_t stream, const DError& E);
+
+}  // namespace jt

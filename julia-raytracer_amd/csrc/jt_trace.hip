@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "jt_denoise.h"
+#include "jt_error.h"
 #include "jt_internal.h"
 #include "jt_kernels.h"
 #include "jt_layout.h"
@@ -136,6 +137,13 @@ struct jt_ctx {
     float4* dn[3] = {nullptr, nullptr, nullptr};
     std::vector<float> dn_host;
     bool denoised = false;  // the result is the filter of the current running means
+    // the error estimate (jt_get_variance, jt_get_noise; jt_error.hip): the per-pixel variance of
+    // the mean, float4[W*H], and one (V, M) pair per workgroup; allocated (the variance zeroed) by
+    // the first call and kept across jt_reset. err_noise is the scalar of the current samples
+    float4* err_var = nullptr;
+    float2* err_sums = nullptr;
+    double err_noise = 0;
+    bool err_valid = false;  // err_var and err_noise are those of the current running means
 };
 
 namespace jtk {
@@ -799,6 +807,7 @@ int finish_aovs(jt_ctx* c) {
 int jt_reset(jt_ctx* c) {
     if (!c) return jt::fail(JT_ERR_INVALID, "ctx is NULL");
     c->denoised = false;
+    c->err_valid = false;
     if (!c->sub.empty()) {
         for (jt_ctx* s : c->sub) {
             const int st = jt_reset(s);
@@ -1095,6 +1104,7 @@ int jt_trace_range(jt_ctx* c, int32_t s0, int32_t s1) {
         return jt::fail(JT_ERR_STATE, "samples must be accumulated in order (expected " + std::to_string(c->next) + ")");
     if (c->first < 0) c->first = s0;
     c->denoised = false;  // jt_get_denoised never returns the filter of fewer samples
+    c->err_valid = false;
     // queue the range behind the deferred ones (jt_ctx::pend0); trace them all once enough are
     // queued, the render is complete (params.samples: the end of Jtrace.main's loop), or a caller
     // reads the accumulators in place (jt_get_device_buffers: it sees every range at once)
@@ -1251,6 +1261,94 @@ int jt_get_denoised(jt_ctx* c, float* rgba) {
     (void)hipSetDevice(c->device);
     hipError_t e = hipMemcpy(rgba, c->dn[2], np * 16, hipMemcpyDeviceToHost);
     return e == hipSuccess ? JT_OK : hip_fail(e, "hipMemcpy denoised");
+}
+
+namespace {
+// The error estimate of the current samples (include/jtrace.h jt_get_variance): checks, the flush,
+// then one launch of error_kernel over the stream means the last combine read, unless the
+// result of these samples is already there. Neither counted in jt_counters nor touching an
+// accumulator or a stream mean.
+int estimate_error(jt_ctx* c) {
+    if (!c->sub.empty())
+        return jt::fail(JT_ERR_UNSUPPORTED,
+                        "the error estimate is not available on a multi-device context (jt_create_multi): "
+                        "query one context per device");
+    if (c->failed) return jt::fail(JT_ERR_STATE, "a previous launch failed; jt_reset the context");
+    const char* need = "the error estimate needs two sample streams that hold a sample";
+    if (c->lk == 0)
+        return jt::fail(JT_ERR_STATE, std::string(need) + ": this context has one (create it with batch >= 2 or "
+                                                          "the option streams)");
+    if (const int st = flush(c)) return st;
+    const long long n = c->first < 0 ? 0 : c->next - c->first;
+    if (n < 1) return jt::fail(JT_ERR_STATE, "no sample has been traced");
+    if (n < 2)
+        return jt::fail(JT_ERR_STATE, std::string(need) + ": one sample has been traced (batch >= 2 or the option "
+                                                          "streams, and two samples)");
+    if (c->err_valid) return JT_OK;
+    (void)hipSetDevice(c->device);
+    const size_t np = (size_t)c->width * c->height;
+    const int tiles = launch_tiles(c->P), nblk = jt::error_blocks(tiles);
+    int st;
+    hipError_t e;
+    if (!c->err_var) {
+        void *var = nullptr, *sums = nullptr;
+        if ((st = device_alloc(c, np * 16, "error estimate", &var)) ||
+            (st = device_alloc(c, std::max<size_t>(1, (size_t)nblk) * sizeof(float2), "error estimate", &sums)))
+            return st;
+        // a tile share's other pixels stay 0
+        if ((e = hipMemsetAsync(var, 0, np * 16, c->stream)) != hipSuccess) return hip_fail(e, "hipMemsetAsync");
+        c->err_var = (float4*)var;
+        c->err_sums = (float2*)sums;
+    }
+    if ((st = zero_if_stale(c))) return st;
+    jt::DError E{};
+    E.part_img = c->A.part_img;
+    E.image = c->A.image;
+    E.var = c->err_var;
+    E.block_sums = c->err_sums;
+    E.nslot = c->A.nslot;
+    E.width = c->width;
+    E.height = c->height;
+    E.tiles = tiles;
+    E.tile_stride = c->P.tile_stride;
+    E.tile_offset = c->P.tile_offset;
+    E.ns = c->aov_cw.ns;  // min(n, k) >= 2, with the weights the image was combined with
+    std::memcpy(E.w, c->aov_cw.w, sizeof E.w);
+    std::vector<float2> sums((size_t)nblk);
+    if ((e = jt::error_launch(c->stream, E)) != hipSuccess || (e = hipStreamSynchronize(c->stream)) != hipSuccess ||
+        (nblk > 0 && (e = hipMemcpy(sums.data(), c->err_sums, sums.size() * sizeof(float2), hipMemcpyDeviceToHost)) != hipSuccess))
+        return hip_fail(e, "error estimate");
+    double V = 0, M = 0;
+    for (const float2& s : sums) V += (double)s.x, M += (double)s.y;
+    // N: the traced pixels inside the image (edge tiles are clipped)
+    const int tiles_x = (c->width + 7) / 8;
+    long long N = 0;
+    for (int u = 0; u < tiles; u++) {
+        const int t = u * c->P.tile_stride + c->P.tile_offset;
+        const int x0 = (t % tiles_x) * 8, y0 = (t / tiles_x) * 8;
+        N += (long long)std::min(8, c->width - x0) * std::min(8, c->height - y0);
+    }
+    c->err_noise = M == 0 ? 0.0 : std::sqrt(3.0 * (double)N * V) / M;
+    c->err_valid = true;
+    return JT_OK;
+}
+}  // namespace
+
+int jt_get_variance(jt_ctx* c, float* var_rgba) {
+    if (!c) return jt::fail(JT_ERR_INVALID, "ctx is NULL");
+    if (!var_rgba) return jt::fail(JT_ERR_INVALID, "var_rgba is NULL");
+    if (const int st = estimate_error(c)) return st;
+    (void)hipSetDevice(c->device);
+    hipError_t e = hipMemcpy(var_rgba, c->err_var, (size_t)c->width * c->height * 16, hipMemcpyDeviceToHost);
+    return e == hipSuccess ? JT_OK : hip_fail(e, "hipMemcpy variance");
+}
+
+int jt_get_noise(jt_ctx* c, double* noise) {
+    if (!c) return jt::fail(JT_ERR_INVALID, "ctx is NULL");
+    if (!noise) return jt::fail(JT_ERR_INVALID, "noise is NULL");
+    if (const int st = estimate_error(c)) return st;
+    *noise = c->err_noise;
+    return JT_OK;
 }
 
 int jt_get_counters(jt_ctx* c, jt_counters* out) {

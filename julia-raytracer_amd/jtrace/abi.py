@@ -287,6 +287,8 @@ def _declare(lib):
     lib.jt_get_denoised.argtypes = [C.c_void_p, f32p]
     lib.jt_denoise_image.argtypes = [f32p, f32p, f32p, C.c_int32, C.c_int32, C.POINTER(jt_denoise_params),
                                      C.c_int32, f32p]
+    lib.jt_get_variance.argtypes = [C.c_void_p, f32p]
+    lib.jt_get_noise.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     lib.jt_reset.argtypes = [C.c_void_p]
     lib.jt_get_device_buffers.argtypes = [C.c_void_p, C.POINTER(jt_device_buffers)]
     lib.jt_set_counters.argtypes = [C.c_void_p, C.c_int32]
@@ -304,6 +306,7 @@ EXPORTED_SYMBOLS = [
     "jt_trace_samples", "jt_trace_range", "jt_get_streams", "jt_get_samples", "jt_get_size", "jt_get_image",
     "jt_get_aovs", "jt_get_counters", "jt_reset", "jt_get_device_buffers", "jt_set_counters", "jt_describe", "jt_synchronize",
     "jt_destroy", "jt_denoise_defaults", "jt_denoise", "jt_get_denoised", "jt_denoise_image",
+    "jt_get_variance", "jt_get_noise",
 ]
 
 

@@ -4,7 +4,9 @@ ArgParse table (:12-86), the SAMPLER_TYPES index (:88) and Params (:90-138).
 Extensions beyond the reference (all optional): --seed (RNG seed), --width/--height (explicit
 image size, camera aspect := W/H), --device, --devices N (one context over GPUs 0..N-1:
 jt_create_multi), --missing (drop|error for incomplete scenes), --traversal (reference|near|wide|auto:
-the BVH traversal, include/jtrace.h jt_traversal).
+the BVH traversal, include/jtrace.h jt_traversal), --noise-target / --noise-interval (stop at an
+estimated relative RMS error, jt_get_noise) and --error-output (the per-pixel standard error as a
+second image, jt_get_variance).
 """
 from __future__ import annotations
 
@@ -62,7 +64,30 @@ def _parser() -> argparse.ArgumentParser:
                    help="BVH traversal (extension): auto (default: wide for deep scenes in HBM, near otherwise), near "
                         "(binary, near child first), wide (4-wide quantised records) or reference (the "
                         "reference's far-first order); images differ only where two hits tie at exactly equal t")
+    p.add_argument("--noise-target", type=float, default=0.0,
+                   help="stop once the image's estimated relative RMS error (jt_get_noise) is at most this; "
+                        "0: off (extension; needs --batch >= 2)")
+    p.add_argument("--noise-interval", type=int, default=16,
+                   help="samples between two checks of --noise-target (extension)")
+    p.add_argument("--error-output", type=str, default="",
+                   help="also save the per-pixel standard error, sqrt of jt_get_variance, to this file "
+                        "(extension; needs --batch >= 2)")
     return p
+
+
+def _check_error_flags(parser: argparse.ArgumentParser, ns) -> None:
+    """The error-estimate extensions need a context with two sample streams or more on one device."""
+    if ns.noise_target < 0 or ns.noise_target != ns.noise_target:
+        parser.error(f"--noise-target must be >= 0 (0: off), got {ns.noise_target}")
+    if ns.noise_interval < 1:
+        parser.error(f"--noise-interval must be at least 1, got {ns.noise_interval}")
+    for flag, used in (("--noise-target", ns.noise_target > 0), ("--error-output", ns.error_output != "")):
+        if used and ns.batch < 2:
+            parser.error(f"{flag} needs two sample streams per pixel: --batch {ns.batch} renders with one; "
+                         "pass --batch 2 or more")
+        if used and ns.devices > 1:
+            parser.error(f"{flag} is not available with --devices {ns.devices}: the error estimate is per "
+                         "device; pass --devices 1")
 
 
 @dataclass
@@ -92,6 +117,9 @@ class Params:
     devices: int = 1
     missing: str = "error"
     traversal: str = DEFAULT_TRAVERSAL
+    noise_target: float = 0.0
+    noise_interval: int = 16
+    error_output: str = ""
 
 
 def params_from_dict(d: dict) -> Params:
@@ -109,5 +137,7 @@ def params_from_dict(d: dict) -> Params:
 
 def parse_cli_args(args) -> Params:
     """parse_cli_args (src/cli.jl:140-147)."""
-    ns = _parser().parse_args(list(args))
+    parser = _parser()
+    ns = parser.parse_args(list(args))
+    _check_error_flags(parser, ns)
     return params_from_dict(vars(ns))

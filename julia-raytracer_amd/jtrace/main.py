@@ -11,6 +11,8 @@ import math
 import sys
 import time
 
+import numpy as np
+
 from . import abi
 from .cli import Params, parse_cli_args
 from .scene import find_camera
@@ -60,6 +62,12 @@ def run(params: Params, out=print) -> dict:
     state = make_trace_state(scene_abi, bvh, lights, jp, lib, devices=list(range(devices)) if devices > 1 else None)
     out("tracing samples...")
     sampling_start = time.perf_counter()
+    # --noise-target: the estimated relative RMS error of the image (jt_get_noise) is checked once
+    # max(2, interval) samples are done and every `interval` samples from then on
+    noise_target = float(getattr(params, "noise_target", 0.0) or 0.0)
+    noise_interval = int(getattr(params, "noise_interval", 16))
+    error_output = getattr(params, "error_output", "") or ""
+    checked = 0
     for _ in range(0, params.samples, params.batch):
         batch_start = time.perf_counter()
         state.trace_samples()
@@ -68,8 +76,16 @@ def run(params: Params, out=print) -> dict:
         etc = (now - sampling_start) / max(done, 1) * (params.samples - done)
         out(f"sample {done:3d}/{params.samples:3d} in {format_seconds(now - batch_start)} "
             f"ETC: {format_seconds(etc)}")
+        if noise_target > 0 and done >= max(2, noise_interval) and done - checked >= noise_interval:
+            checked = done
+            noise = state.noise()
+            out(f"noise {noise:.4f} at {done} samples")
+            if noise <= noise_target:
+                out(f"noise target reached at {done}/{params.samples} samples")
+                break
     render_s = time.perf_counter() - sampling_start
     out(f"rendered in {format_seconds(render_s)} ({render_s:.3f}s)")
+    samples_traced = state.samples
     if params.denoise:  # the a-trous filter over the albedo and normal means (jt_denoise)
         out("denoising...")
         t0 = time.perf_counter()
@@ -80,10 +96,18 @@ def run(params: Params, out=print) -> dict:
         image = state.get_image()
     save_image(params.output, image, state.width, state.height)
     out(f"saved image to {params.output}")
+    if error_output:  # the per-pixel standard error of the image: sqrt of the variance of the mean
+        error = np.sqrt(state.variance())
+        error[..., 3] = 1.0
+        save_image(error_output, error, state.width, state.height)
+        out(f"saved error image to {error_output}")
     out(f"total time: {format_seconds(time.perf_counter() - render_start)}")
     counters = state.counters()
+    result = {"render_s": render_s, "width": state.width, "height": state.height, "counters": counters,
+              "samples_traced": samples_traced}
+    if noise_target > 0 or error_output:
+        result["noise"] = state.noise()  # of the image saved (the last check's value when it stopped the loop)
     state.close()
-    result = {"render_s": render_s, "width": state.width, "height": state.height, "counters": counters}
     if params.denoise:
         result["denoised"] = True
     return result

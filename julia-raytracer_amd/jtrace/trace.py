@@ -7,6 +7,7 @@
     get_image(state)                src/trace.jl:676   -> jt_get_image
     state.denoise() / denoise_image / denoise_defaults (the build's own) -> jt_denoise, jt_get_denoised,
                                                        jt_denoise_image, jt_denoise_defaults
+    state.variance() / state.noise() (the build's own) -> jt_get_variance, jt_get_noise
 
 There is no CPU fallback anywhere in this module: every call goes through libjtrace_hip.so.
 """
@@ -157,6 +158,21 @@ class TraceState:
         out = np.empty((self.height, self.width, 4), np.float32)
         abi.check(self.lib, self.lib.jt_get_denoised(self.handle, out.ctypes.data_as(abi.f32p)))
         return out
+
+    def variance(self) -> np.ndarray:
+        """jt_get_variance: the (H, W, 4) float32 variance of the image per channel (of the mean,
+        not of one sample), from the spread of the sample streams' means. Needs k > 1 streams
+        and two samples (include/jtrace.h)."""
+        out = np.empty((self.height, self.width, 4), np.float32)
+        abi.check(self.lib, self.lib.jt_get_variance(self.handle, out.ctypes.data_as(abi.f32p)))
+        return out
+
+    def noise(self) -> float:
+        """jt_get_noise: the image's relative RMS error, sqrt(mean channel variance) / mean
+        channel value over the pixels this context traces."""
+        v = C.c_double()
+        abi.check(self.lib, self.lib.jt_get_noise(self.handle, C.byref(v)))
+        return v.value
 
     def counters(self) -> dict:
         c = abi.jt_counters()
