@@ -1,0 +1,136 @@
+// jt_context.h — the device context behind include/jtrace.h's jt_ctx and the few functions its
+// pieces share: jt_trace.hip (creation, the sample queue, the getters), jt_multi.hip (the
+// multi-device context), jt_denoise.hip and jt_error.hip (their context halves). Not part of the ABI.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <vector>
+
+#include "jt_internal.h"
+#include "jt_kernels.h"
+
+namespace jtc {
+struct MultiCtx;  // jt_multi.hip
+}
+
+struct jt_ctx {
+    // ---- launch state: the device, the scene and what selects and feeds the trace kernel
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    jtd::DScene S{};
+    jtd::DParams P{};
+    jtk::DAccum A{};
+    std::vector<void*> allocations;
+    int width = 0, height = 0;
+    int total_samples = 0, batch = 1, sampler = 1;
+    int cus = 256;   // compute units of the device (persistent grid size)
+    int lk = 0;      // log2 of the sample streams per pixel (DParams::lk; fixed at jt_create)
+    int tiles = 0;   // 8x8 pixel tiles
+    int stack = 16;  // stack bound of the scene (entries); > 16: LDS ring of `ring` + HBM overflow
+    int ring = 16;
+    int feat = jtd::FT_ALL;   // scene feature bits (jt_records.h)
+    int kmask = jtd::FT_ALL;  // feature mask of the kernel specialisation the scene runs
+    bool wide = false;   // JT_TRAVERSAL_WIDE: the wide-record kernels (configurations 8-15)
+    int traversal = 0;   // jt_params.traversal as resolved (JT_TRAVERSAL_AUTO: near or wide)
+    bool env_alias = false;    // JT_ENV_ALIAS=1: environment lights sample through alias tables
+                               // until jt_reset
+    size_t lds_scene_bytes = 0;  // > 0: small-scene LDS mode
+    int count = 1;             // 1: all traversal counters (diagnostic), 0: paths/rays/light queries only
+    bool exported = false;  // jt_get_device_buffers handed out the accumulators' device pointers
+    bool failed = false;       // a launch failed: the running means are unusable
+    bool stale = true;         // the accumulators are not yet zeroed or overwritten since jt_reset
+    // k > 1: the last launch combined the image only; albedo, normal and hits are combined from
+    // the stream means (weights last_cw) when first read (finish_aovs)
+    bool aov_pending = false;
+    jtk::DCombine last_cw{};  // the weights of the last combine (finish_aovs, the error estimate)
+    unsigned long long launches = 0;
+    double kernel_ms = 0;
+
+    // ---- deferred queue
+    int first = -1, next = 0;  // running-mean origin and next expected sample (deferred ones included)
+    // Deferred samples [pend0, pend1): jt_trace_range / jt_trace_samples queue their range and
+    // trace it, merged with the ranges queued before it, once JT_DEFER_SAMPLES are queued or when
+    // anything reads the context (flush). A render split into calls gives the bits of one call
+    // (jt_trace_range's contract), so merging changes only the launch count: the reference's
+    // default --batch 1 (one call per sample) runs as launches of many samples each.
+    int pend0 = 0, pend1 = 0;
+
+    // ---- one-stream chunks
+    // one-stream contexts (lk == 0): a flushed range of m > 1 samples runs as chunks of up to
+    // `chunk` samples, each traced as one-sample streams into the stream-mean buffers (allocated at
+    // the first such flush) and folded into the running mean by chain_kernel in sample order
+    int chunk = 0;
+    // two sets of chunk buffers: chunk i traces into set i & 1 on `stream` while chain_kernel folds
+    // chunk i - 1 on `stream2` (the chains stay in sample order on stream2; a trace reuses a set
+    // only after the chain that read it, chain_done)
+    float4* cpart[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
+    hipStream_t stream2 = nullptr;
+    hipEvent_t trace_done[2] = {nullptr, nullptr}, chain_done[2] = {nullptr, nullptr};
+
+    // ---- denoise
+    // the denoiser (jt_denoise, jt_denoise.hip): two scratch buffers and the result, float4[W*H]
+    // each, allocated by the first jt_denoise and kept across jt_reset. A multi-device context
+    // filters the reduced host arrays on device 0 and keeps the result on the host instead
+    float4* dn[3] = {nullptr, nullptr, nullptr};
+    bool denoised = false;  // the result is the filter of the current running means
+
+    // ---- error
+    // the error estimate (jt_get_variance, jt_get_noise; jt_error.hip): the per-pixel variance of
+    // the mean, float4[W*H], and one (V, M) pair per workgroup; allocated (the variance zeroed) by
+    // the first call and kept across jt_reset. err_noise is the scalar of the current samples
+    float4* err_var = nullptr;
+    float2* err_sums = nullptr;
+    double err_noise = 0;
+    bool err_valid = false;  // err_var and err_noise are those of the current running means
+
+    // ---- a multi-device context (jt_create_multi) owns its sub-contexts and reduce state here
+    // and uses, of the fields above, only the size, the sample counts, the queue, `failed`,
+    // `denoised`, the counters' totals, and device 0's `lk` and `exported`
+    jtc::MultiCtx* multi = nullptr;
+};
+
+namespace jtc {
+
+int hip_fail(hipError_t e, const char* what);
+// hipMalloc owned by the context (freed by jt_destroy); JT_ERR_NOMEM "hipMalloc <what>"
+int device_alloc(jt_ctx* c, size_t bytes, const char* what, void** p);
+// zeroes the accumulators if nothing has since jt_reset (jt_ctx::stale)
+int zero_if_stale(jt_ctx* c);
+// the deferred AOV combine of the last launch (jt_ctx::aov_pending), before albedo, normal or
+// hits are read: jt_get_aovs, jt_synchronize, jt_get_device_buffers
+int finish_aovs(jt_ctx* c);
+// enqueue the launches of global samples [s0, s1) of a context whose local samples start at `first`
+int trace_launch(jt_ctx* c, int32_t s0, int32_t s1, int32_t first);
+// wait for the launch; its device time in *ms
+int trace_finish(jt_ctx* c, float* ms);
+// trace the deferred samples [pend0, pend1) (jt_ctx) and wait for them; every call that reads
+// the context's results or device buffers runs this first
+int flush(jt_ctx* c);
+
+// xyz of np float4 to np x 3 floats (the AOV getters)
+inline void unpack3(const std::vector<float4>& src, float* dst) {
+    for (size_t k = 0; k < src.size(); k++) {
+        dst[3 * k] = src[k].x;
+        dst[3 * k + 1] = src[k].y;
+        dst[3 * k + 2] = src[k].z;
+    }
+}
+
+// the multi-device branch of the ABI functions (jt_multi.hip), each called as
+// `if (c->multi) return multi_...`, after the checks both kinds of context share
+void multi_destroy(jt_ctx* c);
+int multi_reset(jt_ctx* c);
+int multi_trace_range(jt_ctx* c, int32_t s0, int32_t s1);
+int multi_get_image(jt_ctx* c, float* rgba);
+int multi_get_aovs(jt_ctx* c, float* albedo, float* normal, int64_t* hits);
+int multi_denoise(jt_ctx* c, const jt_denoise_params& p);
+int multi_get_denoised(jt_ctx* c, float* rgba);
+int multi_get_counters(jt_ctx* c, jt_counters* out);
+int multi_get_device_buffers(jt_ctx* c, jt_device_buffers* out);
+int multi_describe(const jt_ctx* c, char* buf, int32_t n);
+int multi_set_counters(jt_ctx* c, int32_t level);
+int multi_synchronize(jt_ctx* c);
+
+}  // namespace jtc

@@ -1,5 +1,5 @@
-// jt_denoise.h — the denoiser's entry points for the device context (jt_trace.hip); the filter,
-// its kernels and jt_denoise_image are in jt_denoise.hip. Not part of the ABI.
+// jt_denoise.h — the denoiser's checks and launch; the filter, its kernels, jt_denoise_image and
+// the context's half (jt_denoise, jt_get_denoised) are in jt_denoise.hip. Not part of the ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>

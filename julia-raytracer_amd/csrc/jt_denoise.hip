@@ -15,6 +15,7 @@
 #include <string>
 #include <vector>
 
+#include "jt_context.h"
 #include "jt_denoise.h"
 
 namespace jtk {
@@ -204,6 +205,46 @@ int jt_denoise_image(const float* rgba, const float* albedo, const float* normal
         e = hipMemcpy(out_rgba, d + 5 * np, np * 16, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return jt::fail(JT_ERR_DEVICE, std::string("denoise: ") + hipGetErrorString(e));
     return JT_OK;
+}
+
+// ---- the context's half (jt_context.h): the filter of a context's running means, kept in jt_ctx::dn
+int jt_denoise(jt_ctx* c, const jt_denoise_params* params) {
+    using namespace jtc;
+    if (!c) return jt::fail(JT_ERR_INVALID, "ctx is NULL");
+    jt_denoise_params p{};
+    if (params) {
+        if (const int st = jt::denoise_check_params(params)) return st;
+        p = *params;
+    }
+    if (c->failed) return jt::fail(JT_ERR_STATE, "a previous launch failed; jt_reset the context");
+    if (const int st = flush(c)) return st;
+    const int samples = c->first < 0 ? 0 : c->next - c->first;
+    if (samples < 1) return jt::fail(JT_ERR_STATE, "no sample has been traced");
+    if (!params) (void)jt_denoise_defaults(samples, &p);
+    c->denoised = false;
+    if (c->multi) return multi_denoise(c, p);
+    const size_t np = (size_t)c->width * c->height;
+    int st;
+    if ((st = zero_if_stale(c)) || (st = finish_aovs(c))) return st;
+    (void)hipSetDevice(c->device);
+    for (int k = 0; k < 3; k++)
+        if (!c->dn[k] && (st = device_alloc(c, np * 16, "denoise buffers", (void**)&c->dn[k]))) return st;
+    // neither counted in jt_counters (launches, kernel_ms) nor touching an accumulator
+    hipError_t e = jt::denoise_launch(c->stream, c->A.image, c->A.albedo, c->A.normal, c->width, c->height, p, c->dn[0],
+                                      c->dn[1], c->dn[2]);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return hip_fail(e, "denoise");
+    c->denoised = true;
+    return JT_OK;
+}
+
+int jt_get_denoised(jt_ctx* c, float* rgba) {
+    if (!c || !rgba) return jt::fail(JT_ERR_INVALID, "NULL argument");
+    if (!c->denoised) return jt::fail(JT_ERR_STATE, "no jt_denoise since the last sample was traced or jt_reset");
+    if (c->multi) return jtc::multi_get_denoised(c, rgba);
+    (void)hipSetDevice(c->device);
+    hipError_t e = hipMemcpy(rgba, c->dn[2], (size_t)c->width * c->height * 16, hipMemcpyDeviceToHost);
+    return e == hipSuccess ? JT_OK : jtc::hip_fail(e, "hipMemcpy denoised");
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
-// jt_error.h — the per-pixel error estimate's entry point for the device context (jt_trace.hip);
-// the kernel is in jt_error.hip. Not part of the ABI.
+// jt_error.h — the per-pixel error estimate's launch; the kernel and the context's half
+// (jt_get_variance, jt_get_noise) are in jt_error.hip. Not part of the ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -10,9 +10,10 @@ namespace jt {
 
 constexpr int ERR_BLOCK = 256;  // threads per workgroup: four 8x8 tiles, as combine_kernel's
 
-// One launch over the slots of a context's stream means (DAccum::part_img, jt_kernels.h), with
-// combine_kernel's indexing: thread g is lane g & 63 of launch tile g >> 6, stream j's record of
-// its pixel is part_img[j * nslot + g].
+// One launch over the slots of a context's stream means (DAccum::part_img, jt_kernels.h): thread
+// g is launch slot g (slot_pixel, jt_plan.h), stream j's record of its pixel is
+// part_img[j * nslot + g]. The launch's share of the tiles is carried here rather than as the
+// context's DParams: the kernel's arguments stay these few words.
 struct DError {
     const float4* part_img;
     const float4* image;      // the combined means, as combine_kernel wrote them

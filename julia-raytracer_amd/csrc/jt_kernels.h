@@ -1596,8 +1596,7 @@ constexpr int NBANDS = 8, BAND_STRIDE = 16;
 
 // number of 8x8 tiles a launch covers (DParams tile_stride / tile_offset)
 __host__ __device__ __forceinline__ int launch_tiles(const DParams& P) {
-    const int all = ((P.width + 7) / 8) * ((P.height + 7) / 8);
-    return all > P.tile_offset ? (all - P.tile_offset + P.tile_stride - 1) / P.tile_stride : 0;
+    return plan_tiles(P.width, P.height, P.tile_stride, P.tile_offset);
 }
 
 // ============================================================================ sample streams + per-lane work items
@@ -1609,7 +1608,7 @@ __host__ __device__ __forceinline__ int launch_tiles(const DParams& P) {
 // items however few pixels it covers, and the launch ends by combining each pixel's stream means
 // in stream order (combine_kernel, weights n_j / n). k = 1 is the reference's own single running
 // mean (the image buffer is stream 0): one sample per launch reads and writes it here; a longer
-// range runs as chunks of one-sample streams folded in sample order (chain_kernel, jt_trace.hip).
+// range runs as chunks of one-sample streams folded in sample order (chain_kernel, jt_accum.hip).
 // Results depend on k (fixed per context, jt_get_streams) and not on how a render is split into
 // calls or launches.
 //
@@ -2061,13 +2060,18 @@ __device__ __forceinline__ void trace_body_items(const DScene& S0, const DParams
     }
 }
 
-// The launch's last step when k > 1 (combine_kernel, jt_trace.hip): each pixel's stream means
+// The launch's last step when k > 1 (combine_kernel, jt_accum.hip): each pixel's stream means
 // combined in stream order, mean = sum_j mean_j * w_j over the streams with samples (w_j = n_j /
 // n, host-computed in double and rounded once), hits = sum_j hits_j.
 struct DCombine {
     float w[JT_MAX_STREAMS];
     int ns;  // streams with samples: min(k, n)
 };
+// the combine after n local samples of a context with 2^lk streams (jt_plan.h)
+inline void combine_weights(long long n, int lk, DCombine& cw) {
+    cw = DCombine{};
+    cw.ns = combine_weights(n, lk, cw.w);
+}
 // Occupancy request (waves per SIMD); JT_WAVES=0 leaves it to the compiler. The LDS-mode
 // FT_NONE kernel (cornellbox: 96 VGPRs, LDS for 5 workgroups per CU with the stack sized to the
 // scene) asks for JT_WAVES_NONE: measured +4 % over 4 waves with its wait_lanes of 56.

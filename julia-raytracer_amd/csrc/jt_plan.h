@@ -1,0 +1,109 @@
+// jt_plan.h — the launch plan of a context as integer functions: which 8x8 tiles a launch covers,
+// which pixel a launch slot is, how many sample streams a context keeps, the stream weights of a
+// combine, the chunk size of a one-stream context and a device's share of a batch. Plain C++ (no
+// HIP runtime), shared by the kernels, the device context and the host check (tests/plan_check.cpp).
+#pragma once
+
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define JT_PLAN_HD __host__ __device__ inline
+#else
+#define JT_PLAN_HD inline
+#endif
+
+// automatic stream count (stream_log2): at least JT_STREAMS_MIN streams — JT_STREAMS_WIDE for a
+// batch of at least two samples per such stream — and JT_STREAM_ITEMS (pixel, stream) items, at
+// most JT_STREAM_ITEMS_MAX items
+#define JT_STREAMS_MIN 16
+#define JT_STREAMS_WIDE 32
+#define JT_STREAM_ITEMS (1LL << 22)
+#define JT_STREAM_ITEMS_MAX (1LL << 27)
+#ifndef JT_MAX_STREAMS
+#define JT_MAX_STREAMS 64  // sample streams per pixel (a power of two, jt_ctx::lk)
+#endif
+
+namespace jtk {
+
+// number of 8x8 tiles a launch covers: tiles offset, offset + stride, ... of the image's
+// (DParams tile_stride / tile_offset)
+JT_PLAN_HD int plan_tiles(int width, int height, int stride, int offset) {
+    const int all = ((width + 7) / 8) * ((height + 7) / 8);
+    return all > offset ? (all - offset + stride - 1) / stride : 0;
+}
+
+// Launch slot g (< plan_tiles * 64) is lane g & 63 of launch tile g >> 6: pixel (i, j) of image
+// tile t = (g >> 6) * tile_stride + tile_offset, row-major within the tile. inside: false for the pixels of
+// an edge tile past the image's width or height.
+struct SlotPixel {
+    int i, j;
+    bool inside;
+};
+JT_PLAN_HD SlotPixel slot_pixel(int g, int width, int height, int tile_stride, int tile_offset) {
+    const int tiles_x = (width + 7) / 8;
+    const int t = (g >> 6) * tile_stride + tile_offset, l = g & 63;
+    const int i = (t % tiles_x) * 8 + (l & 7), j = (t / tiles_x) * 8 + (l >> 3);
+    return SlotPixel{i, j, i < width && j < height};
+}
+
+// the launch slots inside the image: every pixel the launch traces (edge tiles are clipped)
+JT_PLAN_HD long long traced_pixels(int width, int height, int stride, int offset) {
+    const int tiles = plan_tiles(width, height, stride, offset);
+    long long n = 0;
+    for (int u = 0; u < tiles; u++) {
+        const SlotPixel p = slot_pixel(u * 64, width, height, stride, offset);  // the tile's first pixel
+        const int w = width - p.i, h = height - p.j;
+        n += (long long)(w < 8 ? w : 8) * (h < 8 ? h : 8);
+    }
+    return n;
+}
+
+// Sample streams per pixel (DESIGN.md §2 "Sample streams"), fixed at jt_create from the pixels
+// the context traces and the batch only (never from the scene's memory mode, so every option
+// that picks LDS or HBM mode keeps the image bits): 1 for the reference's default one-sample
+// batches (its single running mean); otherwise at least 16 — 32 from a batch of 64 (two samples
+// per stream) — and enough for 2^22 (pixel, stream) items (a context tracing few pixels — a tile
+// share, a small image — still fills the GPU), at most 64, the batch, and 2^27 items of stream
+// means (6.4 GB).
+// Measured (gpurun_out/r05i, r05j): bathroom1 1024 spp 8 -> 16 streams +0.8 %, features2 512 spp
+// +2 %, ecosys 64 spp 2 -> 16 +2.6 %, its 1/8 share (512 spp) +3.7 %; a 1/8 tile share of the
+// headline 32 streams 9265, 64 streams 9794 Mrays/s. A context whose scene runs from HBM starts
+// from 32 streams when the batch gives each at least two samples (gpurun_out/r05sk, r05sk2:
+// features2 +0.6 %, bathroom1 +0.5 %; cornellbox +1.0 %, round 5, when 32 streams were the
+// HBM-mode rule only). The option "streams" overrides.
+JT_PLAN_HD int stream_log2(long long pixels, int batch) {
+    if (batch <= 1) return 0;
+    long long want = batch >= 2 * JT_STREAMS_WIDE ? JT_STREAMS_WIDE : JT_STREAMS_MIN;
+    while (pixels * want < JT_STREAM_ITEMS) want *= 2;
+    int lk = 0;
+    while (lk < 6 && (2LL << lk) <= want && (2 << lk) <= batch && (2 << lk) <= JT_MAX_STREAMS &&
+           pixels * (2LL << lk) <= JT_STREAM_ITEMS_MAX)
+        lk++;
+    return lk;
+}
+
+// weights n_j / n of the k = 2^lk streams after n local samples: stream j holds those t < n with
+// t mod k == j (include/jtrace.h jt_get_streams restates the rule), computed in double and rounded
+// once. Fills w[0 .. ns) and returns ns = min(n, k), the streams that hold a sample.
+JT_PLAN_HD int combine_weights(long long n, int lk, float* w) {
+    const long long k = 1LL << lk;
+    const int ns = (int)(n < k ? n : k);
+    for (int j = 0; j < ns; j++) w[j] = (float)((double)((n - 1 - j) / k + 1) / (double)n);
+    return ns;
+}
+
+// the chunk size of a one-stream context whose launches cover nslot slots: as many one-sample
+// streams as two sets of stream-mean buffers hold, at most 64 (JT_MAX_STREAMS) and 2^27 (stream,
+// slot) records in all (6.4 GB). 1: none possible.
+JT_PLAN_HD int chunk_samples(long long nslot) {
+    int m = JT_MAX_STREAMS;
+    while (m > 1 && 2 * nslot * m > JT_STREAM_ITEMS_MAX) m >>= 1;
+    return m;
+}
+
+// the contiguous share [*a, *b) of device d of D of the batch [s0, s1) under the sample split
+JT_PLAN_HD void sample_share(int s0, int s1, int d, int D, int* a, int* b) {
+    const long long L = s1 - s0;
+    *a = s0 + (int)(L * d / D);
+    *b = s0 + (int)(L * (d + 1) / D);
+}
+
+}  // namespace jtk

@@ -6,21 +6,13 @@
 #include <hip/hip_vector_types.h>
 #include <stdint.h>
 
-// automatic stream count (jt_trace.hip stream_log2): at least JT_STREAMS_MIN streams —
-// JT_STREAMS_WIDE for a batch of at least two samples per such stream — and JT_STREAM_ITEMS
-// (pixel, stream) items, at most JT_STREAM_ITEMS_MAX items
-#define JT_STREAMS_MIN 16
-#define JT_STREAMS_WIDE 32
-#define JT_STREAM_ITEMS (1LL << 22)
-#define JT_STREAM_ITEMS_MAX (1LL << 27)
+#include "jt_plan.h"  // the stream-count constants (JT_MAX_STREAMS, JT_STREAM_ITEMS_MAX, ...)
+
 #ifndef JT_AUTO_WIDE_MIN_STACK
 #define JT_AUTO_WIDE_MIN_STACK 32  // JT_TRAVERSAL_AUTO: wide records for HBM-mode scenes deeper than this
 #endif
 // jt_trace_range defers its range until this many samples are queued (jt_ctx::pend0)
 #define JT_DEFER_SAMPLES 64
-#ifndef JT_MAX_STREAMS
-#define JT_MAX_STREAMS 64  // sample streams per pixel (a power of two, jt_ctx::streams)
-#endif
 #ifndef JT_EXACT_MATH
 #define JT_EXACT_MATH 1
 #endif
@@ -209,12 +201,12 @@ struct DParams {
     int first;  // running-mean origin: local sample t = s - first
     // sample streams (DESIGN.md §2 "Sample streams"): local sample t belongs to stream
     // t & (2^lk - 1) and is the (t >> lk)-th sample of that stream's own running mean, weight
-    // 1/((t >> lk) + 1); the launch ends by combining the streams' means (jt_trace.hip combine)
+    // 1/((t >> lk) + 1); the launch ends by combining the streams' means (jt_accum.hip combine)
     int lk;
     int wait_lanes;
     int light_lanes;  // path sampler: run a light-hit step inside the traversal phase once this
                       // many lanes wait on a sample_lights_pdf query result (65: never)
-    // the 8x8 tiles this launch covers: t = k * tile_stride + tile_offset (a multi-device context
+    // the 8x8 tiles this launch covers: every tile_stride-th from tile_offset (a multi-device context
     // split by pixel tiles, jt_create_multi; 1 / 0 otherwise: every tile)
     int tile_stride, tile_offset;
     unsigned long long seed;

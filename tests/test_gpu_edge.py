@@ -72,6 +72,45 @@ def test_ragged_framings_match_the_oracle(gpu, abi, lib, oracle, cornell_abi, w,
     st.close()
 
 
+@pytest.mark.parametrize("share", [None, "4,3"])
+def test_one_stream_chunk_on_partial_edge_tiles(gpu, abi, lib, cornell_abi, options, share):
+    """chain_kernel (csrc/jt_accum.hip) on partial edge tiles under a tile share: 44x36 (6x5 tiles,
+    the last column and row 4 pixels wide), one stream, 5 samples of the path sampler. A context
+    that reads the image after every sample flushes each time (one launch per sample, no chain);
+    one that queues all 5 and reads once runs them as one chunk folded by chain_kernel. Image,
+    albedo, normal and hits are equal bit for bit, and under the share "4,3" every pixel outside
+    tiles 3, 7, ..., 27 is zero."""
+    from jtrace import trace
+    options("tile_share", share)
+    params = make_params(abi, width=44, height=36, samples=5, batch=1, sampler=1)
+    bvh = trace.make_scene_bvh(cornell_abi, False, lib)
+    lights = trace.make_trace_lights(cornell_abi, lib)
+    outs = []
+    for per_sample in (True, False):
+        st = trace.make_trace_state(cornell_abi, bvh, lights, params, lib)
+        assert st.streams == 1, st.describe()
+        for _ in range(5):
+            st.trace_samples()
+            if per_sample:
+                st.get_image()
+        assert st.samples == 5
+        outs.append((st.get_image(), *st.get_aovs(), st.counters()["launches"]))
+        st.close()
+    exp, got = outs
+    assert exp[4] == 5 and got[4] == 1, (exp[4], got[4])  # per-sample launches against one chunk
+    for a, b, name in zip(exp[:4], got[:4], ("image", "albedo", "normal", "hits")):
+        assert np.array_equal(a, b), name
+    assert got[3].sum() > 0 and got[0][..., :3].max() > 0, "the share's tiles must be hit and lit"
+    if share:
+        ty, tx = np.divmod(np.arange(30), 6)
+        mask = np.zeros((36, 44), bool)
+        for t in range(3, 30, 4):
+            mask[ty[t] * 8:ty[t] * 8 + 8, tx[t] * 8:tx[t] * 8 + 8] = True
+        for a, name in zip(got[:4], ("image", "albedo", "normal", "hits")):
+            assert np.all(a[~mask] == 0), name
+        assert np.any(got[0][mask] != 0)
+
+
 def _rotation(rng):
     q, r = np.linalg.qr(rng.normal(size=(3, 3)))
     return q * np.sign(np.diag(r))

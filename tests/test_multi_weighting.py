@@ -1,4 +1,4 @@
-"""The multi-device context's sharding and weighting (jt_create_multi, csrc/jt_trace.hip
+"""The multi-device context's sharding and weighting (jt_create_multi, csrc/jt_multi.hip
 multi_trace_range / multi_reduce), restated on the CPU oracle: every batch [s0, s1) of the
 reference's batch loop (src/jtrace.jl:83-106) is split into contiguous per-device shares; device
 d appends its share to its own running mean with weight 1/(n_d + k + 1) (the kernel's
