@@ -494,6 +494,35 @@ __device__ __forceinline__ void query_start(const DScene& S, Trav& T, v3 o, v3 d
     if (WIDE) query_begin_wide(S, T, o, d, inst < 0 ? WROOT_SCENE : wroot_instance(inst), rerun);
     else query_begin(S, T, o, d, inst < 0 ? ((T_TLAS << 30) | SNAP_NONE) : ((T_INST << 30) | SNAP_NONE | (unsigned)inst), stack, rerun);
 }
+// The scene query of a lane that has just run its bounce's light chains inline (light_chain with
+// JT_CHAIN_TAIL) in the binary traversal: query_begin for the same direction d, whose world-space
+// 1/d the chain left in T.wdinv and, in kernels without instance transforms, whose push mask it
+// left in T.negmask. The instance-space values of a transformed light (T.ldinv, T.negmask with
+// FT_XFORM) are never reused.
+template <int F>
+__device__ __forceinline__ void query_restart(const DScene& S, Trav& T, v3 o, v3 d, int* stack) {
+    T.wo = o;
+    T.wd = d;
+    T.lo = o;
+    T.ld = d;
+    T.ldinv = T.wdinv;
+    T.tmax = __builtin_inff();
+    T.nh = 0;
+    T.h_inst = -1;
+    T.h_elem = -1;
+    T.h_u = 0;
+    T.h_v = 0;
+    T.nprim = 0;
+    T.prim = 0;
+    T.cur_inst = -1;
+    T.cur_kind = KIND_TRI;
+    T.inst_space = 0;
+    if (F & FT_XFORM) T.negmask = neg_mask(d, S.order_flip);
+    stack[0] = (int)((T_TLAS << 30) | SNAP_NONE);
+    T.sp = 1;
+    T.low = 0;
+    T.nxt = W_EMPTY;
+}
 // a finished near-first query that saw an exact-t tie: run it again in the reference's child order
 // (the same world ray (o, d): every query is started on its path's (st.o, st.d), which do not
 // change until its hit is consumed — so T.wo/T.wd stay dead in kernels without instance
@@ -1071,36 +1100,45 @@ __device__ __forceinline__ bool begin_light_pdf(const DScene& S, const DParams& 
     st.set_lq<F>(st.o);
     return light_advance<F>(S, P, st);
 }
-// one intersect_instance_bvh result of the instance-light loop (src/trace.jl:1024-1044)
+// one intersect_instance_bvh result of the instance-light loop (src/trace.jl:1024-1044), in two
+// parts. A hit (light_hit_add) adds the element's pdf term and moves the query origin behind it;
+// it returns whether the chain goes on (lcount < 100). A miss, or the 100th hit, ends the chain:
+// light_chain_end adds the chain's sum and walks on through the light list.
 template <int F>
-__device__ __forceinline__ bool light_hit(const DScene& S, const DParams& P, Path& st, const Hit& h) {
-    if (h.hit) {
-        // the light's element record (DLightElem): eval_position + eval_element_normal + the area
-        const int4 lh = row16<F>(S.light_hit + st.li);  // instance, first record
-        const DInstShade& is = S.inst_shade[lh.x];
-        const fr3 f = frame_from(is.f0, is.f1, is.f2);
-        const float4* r = S.light_elems + 5 * (lh.y + h.elem);
-        const float4 r0 = r[0], r1 = r[1], r2 = r[2], r3 = r[3];
-        const v3 p1 = V3(r0.x, r0.y, r0.z), p2 = V3(r0.w, r1.x, r1.y), p3 = V3(r1.z, r1.w, r2.x);
-        const v2 uv = V2(h.u, h.v);
-        v3 lposition;
-        if (!(F & FT_QUAD) || __float_as_int(r3.z) == KIND_TRI) {
-            lposition = transform_point(f, interp_tri(p1, p2, p3, uv));
-        } else {
-            const float4 r4 = r[4];
-            lposition = transform_point(f, interp_quad(p1, p2, p3, V3(r4.x, r4.y, r4.z), uv));
-        }
-        const v3 en = V3(r2.y, r2.z, r2.w);
-        v3 lnormal = __float_as_int(r3.y) ? en : transform_normal(f, en);
-        const float area = r3.x;
-        v3 dd = lposition - st.lq<F>();
-        st.lpdf += dot(dd, dd) / (__builtin_fabsf(dot(lnormal, st.d)) * area);
-        st.o = lposition + st.d * 0.001f;
-        st.ctl += 1u << CTL_LC;  // lcount += 1 (< 100: fits its 7 bits)
-        if (st.lcount() < 100) return false;
+__device__ __forceinline__ bool light_hit_add(const DScene& S, Path& st, const Hit& h) {
+    // the light's element record (DLightElem): eval_position + eval_element_normal + the area
+    const int4 lh = row16<F>(S.light_hit + st.li);  // instance, first record
+    const DInstShade& is = S.inst_shade[lh.x];
+    const fr3 f = frame_from(is.f0, is.f1, is.f2);
+    const float4* r = S.light_elems + 5 * (lh.y + h.elem);
+    const float4 r0 = r[0], r1 = r[1], r2 = r[2], r3 = r[3];
+    const v3 p1 = V3(r0.x, r0.y, r0.z), p2 = V3(r0.w, r1.x, r1.y), p3 = V3(r1.z, r1.w, r2.x);
+    const v2 uv = V2(h.u, h.v);
+    v3 lposition;
+    if (!(F & FT_QUAD) || __float_as_int(r3.z) == KIND_TRI) {
+        lposition = transform_point(f, interp_tri(p1, p2, p3, uv));
+    } else {
+        const float4 r4 = r[4];
+        lposition = transform_point(f, interp_quad(p1, p2, p3, V3(r4.x, r4.y, r4.z), uv));
     }
+    const v3 en = V3(r2.y, r2.z, r2.w);
+    v3 lnormal = __float_as_int(r3.y) ? en : transform_normal(f, en);
+    const float area = r3.x;
+    v3 dd = lposition - st.lq<F>();
+    st.lpdf += dot(dd, dd) / (__builtin_fabsf(dot(lnormal, st.d)) * area);
+    st.o = lposition + st.d * 0.001f;
+    st.ctl += 1u << CTL_LC;  // lcount += 1 (< 100: fits its 7 bits)
+    return st.lcount() < 100;
+}
+template <int F>
+__device__ __forceinline__ bool light_chain_end(const DScene& S, const DParams& P, Path& st) {
     st.pdf += st.lpdf;
     return light_advance<F>(S, P, st);
+}
+template <int F>
+__device__ __forceinline__ bool light_hit(const DScene& S, const DParams& P, Path& st, const Hit& h) {
+    if (h.hit && light_hit_add<F>(S, st, h)) return false;
+    return light_chain_end<F>(S, P, st);
 }
 
 // The light chain of sample_lights_pdf run inline (DScene::light_inline: every instance light's
@@ -1114,6 +1152,37 @@ __device__ __forceinline__ bool light_hit(const DScene& S, const DParams& P, Pat
 #ifndef JT_LIGHT_LEAF_STEP
 #define JT_LIGHT_LEAF_STEP 1  // 0: every inline light query goes through query_start + node_step (A/B runs)
 #endif
+// JT_CHAIN_TAIL: a wave runs the end of a light's chain (light_chain_end: the MIS weight, Russian
+// roulette, the next bounce) once, after all its lanes have left the query loop, instead of in
+// every iteration in which some lane misses. In the kernels whose chains run through
+// inst_leaf_query, 1/d and the push mask are computed by the first query of a bounce's chains
+// only, and the scene query that follows keeps them too (query_restart). Each lane's own sequence
+// of operations is unchanged. 0: the previous loops; 1: the chain's end once, 1/d per query as
+// before (A/B runs).
+// Adopted per kernel family where measured not slower (EXPERIMENTS.md): not in the wide kernels
+// (not measured), not in FT_MESH's (bathroom1: -0.6 %, its chains keep the re-run loop); the light-steps kernel
+// (FT_NONE without FT_LINL) never runs a chain inline (kernel_mask) and keeps its compiled form.
+#ifndef JT_CHAIN_TAIL
+#define JT_CHAIN_TAIL 2
+#endif
+// the FT_MESH kernel (bathroom1's), with or without FT_LINL
+__host__ __device__ constexpr bool ft_mesh_kernel(int F) {
+    return (F & ~FT_LINL) == (FT_TEX | FT_ATTR | FT_MAT | FT_OPAC | FT_XFORM);
+}
+template <bool WIDE, int F>
+__host__ __device__ constexpr bool chain_tail() {
+    return JT_CHAIN_TAIL && !WIDE && !(F & FT_NOIL) && F != FT_NONE && !ft_mesh_kernel(F);
+}
+// the chains run through inst_leaf_query: the binary fixed-stack LDS kernels (not FT_MESH's)
+template <bool WIDE, bool OVF, bool NCACHE, int F>
+__host__ __device__ constexpr bool chain_leaf_step() {
+    return JT_LIGHT_LEAF_STEP && !WIDE && !OVF && !NCACHE && !ft_mesh_kernel(F);
+}
+// 1/d and the push mask once per bounce, in the query state (light_chain, query_restart)
+template <bool WIDE, bool OVF, bool NCACHE, int F>
+__host__ __device__ constexpr bool chain_dinv_once() {
+    return JT_CHAIN_TAIL >= 2 && chain_tail<WIDE, F>() && chain_leaf_step<WIDE, OVF, NCACHE, F>();
+}
 // One query of an inline chain in the binary fixed-stack LDS kernels: intersect_instance_bvh of an
 // instance whose BLAS is one leaf (INST_LEAF_ROOT), without the stack round trip of query_start +
 // node_step — the instance record and its root node are read directly, the root box is tested by
@@ -1168,29 +1237,46 @@ __device__ __forceinline__ bool light_chain(const DScene& S, const DParams& P, P
     // No tie re-run is needed here: a one-leaf BLAS has no child order (INST_LEAF_ROOT). The
     // FT_MESH kernel (bathroom1) keeps the re-run loop anyway, never taken: its compiled
     // layout is 4 % faster with it, features2's kernel 1.5 % slower (gpurun_out/r05v)
-    constexpr bool RERUN_LOOP = (F & ~FT_LINL) == (FT_TEX | FT_ATTR | FT_MAT | FT_OPAC | FT_XFORM);  // FT_MESH
-    if (JT_LIGHT_LEAF_STEP && !WIDE && !OVF && !NCACHE && !RERUN_LOOP) {
-        // st.d does not change while the chain runs (light_hit moves st.o only): 1/d and the push
-        // mask of every query of the chain are computed once
-        do {
-            count_lq();
-            const v3 d = st.d;
-            const v3 dinv = V3(jl_rcp(d.x), jl_rcp(d.y), jl_rcp(d.z));  // ray_dinv (src/bvh.jl:322), no guard
-            const int negmask = neg_mask(d, S.order_flip);
-            inst_leaf_query<COUNT, F>(S, T, st.o, d, dinv, negmask, S.lights[st.li].instance, cnt);
-            while (T.nprim > 0) prim_step<COUNT, F>(S, T, cnt);
-            if (light_hit<F>(S, P, st, query_hit(T))) return true;
-        } while (st.phase == PH_LIGHT);
-        return false;
-    }
-    do {
+    constexpr bool RERUN_LOOP = ft_mesh_kernel(F);
+    constexpr bool LEAF = chain_leaf_step<WIDE, OVF, NCACHE, F>(), TAIL = chain_tail<WIDE, F>();
+    // st.d does not change while the bounce's chains run (light_hit_add moves st.o only): with
+    // DINV_ONCE the first query's 1/d and push mask stay in the query state for the later ones
+    // (with instance transforms a query may leave its instance's mask in T.negmask: not that one)
+    constexpr bool DINV_ONCE = chain_dinv_once<WIDE, OVF, NCACHE, F>();
+    const auto dinv = [&] { T.wdinv = V3(jl_rcp(st.d.x), jl_rcp(st.d.y), jl_rcp(st.d.z)); };  // ray_dinv (src/bvh.jl:322), no guard
+    // one intersect_instance_bvh of the current light
+    const auto query = [&] {
         count_lq();
         const int inst = S.lights[st.li].instance;
-        query_start<WIDE>(S, T, st.o, st.d, inst, stack);
-        do {
-            node_step_any<WIDE, RING, OVF, COUNT, NCACHE, F>(S, T, stack, pixel, cnt);  // instance + its one-leaf root
+        if (LEAF) {
+            if (!DINV_ONCE) dinv();
+            const int negmask = DINV_ONCE && !(F & FT_XFORM) ? T.negmask : neg_mask(st.d, S.order_flip);
+            inst_leaf_query<COUNT, F>(S, T, st.o, st.d, T.wdinv, negmask, inst, cnt);
             while (T.nprim > 0) prim_step<COUNT, F>(S, T, cnt);
-        } while (RERUN_LOOP && rerun_tie<WIDE>(S, T, st.o, st.d, inst, stack));
+        } else {
+            query_start<WIDE>(S, T, st.o, st.d, inst, stack);
+            do {
+                node_step_any<WIDE, RING, OVF, COUNT, NCACHE, F>(S, T, stack, pixel, cnt);  // instance + its one-leaf root
+                while (T.nprim > 0) prim_step<COUNT, F>(S, T, cnt);
+            } while (RERUN_LOOP && rerun_tie<WIDE>(S, T, st.o, st.d, inst, stack));
+        }
+    };
+    if (TAIL) {
+        if (DINV_ONCE) {
+            dinv();
+            if (!(F & FT_XFORM)) T.negmask = neg_mask(st.d, S.order_flip);
+        }
+        for (;;) {
+            // one light's chain: a lane stays while its query hits; then the chain's end, once for
+            // the wave's chain lanes together
+            do query();
+            while (T.h_inst >= 0 && light_hit_add<F>(S, st, query_hit(T)));
+            if (light_chain_end<F>(S, P, st)) return true;
+            if (st.phase != PH_LIGHT) return false;
+        }
+    }
+    do {
+        query();
         if (light_hit<F>(S, P, st, query_hit(T))) return true;
     } while (st.phase == PH_LIGHT);
     return false;
@@ -1948,8 +2034,10 @@ __device__ __forceinline__ void trace_body_items(const DScene& S0, const DParams
             else if (light) done = light_hit<F>(S, P, st, query_hit(T));
             else if (SAMPLER == 2) done = naive_hit<F>(S, P, st, query_hit(T), aov, cnt.shades);
             else done = path_hit<F>(S, P, st, query_hit(T), aov, cnt.shades);
+            bool chained = false;  // the lane ran its bounce's light chains here (query_restart below)
             if (SAMPLER == 1 && !done && st.phase == PH_LIGHT && chains_inline(F, S)) {
                 unsigned nlq = 0;
+                chained = true;
                 done = light_chain<WIDE, RING, OVF, COUNT, NCACHE, F>(S, P, st, T, stack, oslot, cnt, [&] {
                     if (WC) nlq++;
                     else lds_count(2, true);
@@ -2018,7 +2106,13 @@ __device__ __forceinline__ void trace_body_items(const DScene& S0, const DParams
                 } else {
                     if (WC) c_ray = true;
                     else lds_count(1, true);
-                    query_start<WIDE>(S, T, st.o, st.d, -1, stack);
+                    // when every lane of the wave that goes on comes from a chain (none from a delta
+                    // material, none in a scene without instance lights), the wave's scene queries
+                    // keep the chain's 1/d: st.d has not changed since. A wave-uniform choice, so
+                    // only one of the two forms executes.
+                    if (SAMPLER == 1 && chain_dinv_once<WIDE, OVF, NCACHE, F>() && __builtin_amdgcn_ballot_w64(!chained) == 0)
+                        query_restart<F>(S, T, st.o, st.d, stack);
+                    else query_start<WIDE>(S, T, st.o, st.d, -1, stack);
                 }
                 // the query's first pop (TLAS root, or the light instance and its BLAS root) here,
                 // where most of the wave's lanes take part, rather than in a sparser traversal step
