@@ -5,7 +5,7 @@
 
 #include <hip/hip_runtime.h>
 
-#include "jt_kernels.h"
+#include "jt_launch.h"
 
 namespace jt {
 

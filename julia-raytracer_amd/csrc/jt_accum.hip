@@ -8,7 +8,7 @@
 using namespace jtd;
 
 namespace jtk {
-// the combine of every pixel's stream means (DCombine, jt_kernels.h), one thread per pixel of
+// the combine of every pixel's stream means (DCombine, jt_launch.h), one thread per pixel of
 // the launch's tiles (slot g); stream j's records of neighbouring pixels are contiguous (coalesced).
 // Two kernels over the same streams: the image after every launch (16 B per pixel and stream),
 // the AOVs and hits (32 B per pixel and stream) only when they are read (jt_ctx::aov_pending):

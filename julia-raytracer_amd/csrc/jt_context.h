@@ -8,7 +8,7 @@
 #include <vector>
 
 #include "jt_internal.h"
-#include "jt_kernels.h"
+#include "jt_launch.h"
 
 namespace jtc {
 struct MultiCtx;  // jt_multi.hip

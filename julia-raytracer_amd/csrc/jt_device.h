@@ -1,7 +1,7 @@
 // jt_device.h — per-lane math of the MI355X path tracer; the device-side data layout it works on
 // is jt_records.h (plain data, shared with the host layout in jt_layout.cpp).
 //
-// Everything here runs per lane inside the trace megakernel (jt_kernels.h). Each function
+// Everything here runs per lane inside the trace megakernel (jt_kernels.h and the headers it is made of). Each function
 // cites the reference (Princic-1837592/julia-raytracer) source it computes. Float contract
 // (DESIGN.md §Numerics): compiled with -ffp-contract=off (no FMA contraction, Julia's
 // evaluation order), Julia's NaN-propagating min/max, and — in the parity build

@@ -10,7 +10,7 @@ namespace jt {
 
 constexpr int ERR_BLOCK = 256;  // threads per workgroup: four 8x8 tiles, as combine_kernel's
 
-// One launch over the slots of a context's stream means (DAccum::part_img, jt_kernels.h): thread
+// One launch over the slots of a context's stream means (DAccum::part_img, jt_launch.h): thread
 // g is launch slot g (slot_pixel, jt_plan.h), stream j's record of its pixel is
 // part_img[j * nslot + g]. The launch's share of the tiles is carried here rather than as the
 // context's DParams: the kernel's arguments stay these few words.

@@ -1,4 +1,4 @@
-// jt_kv.hip — one kernel configuration of the megakernel (jt_kernels.h, LaunchConfig<JT_VARIANT>),
+// jt_kv.hip — one kernel configuration of the megakernel (jt_kernels.h; LaunchConfig<JT_VARIANT>, jt_launch.h),
 // instantiated for both samplers and both counter levels. The Makefile compiles this file once
 // per configuration (-DJT_VARIANT=0..NUM_LAUNCH_CONFIGS-1), so the kernels build in parallel.
 #include "jt_kernels.h"

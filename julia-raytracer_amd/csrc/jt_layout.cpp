@@ -90,7 +90,7 @@ DNode pack_node(const jt_bvh_node& n, int start) {
 // Conservative 8-bit quantisation of a child's slab [cmin, cmax] on one axis, relative to the
 // record's origin o with scale s (a power of two): the largest lo with o + lo * s <= cmin and the
 // smallest hi with o + hi * s >= cmax, evaluated in the device's float operations (wide_box,
-// jt_kernels.h; -ffp-contract=off on both sides). false: no byte fits at this scale.
+// jt_traverse.h; -ffp-contract=off on both sides). false: no byte fits at this scale.
 bool quantize_axis(float o, float s, float cmin, float cmax, unsigned& lo, unsigned& hi) {
     auto deq = [&](int q) { return o + (float)q * s; };
     int q = (int)std::max(0.0, std::min(255.0, std::floor(((double)cmin - (double)o) / (double)s)));

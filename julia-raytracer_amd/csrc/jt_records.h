@@ -1,5 +1,5 @@
 // jt_records.h — the device records of the MI355X path tracer: what jt_layout.cpp writes on the
-// host and the kernels (jt_device.h, jt_kernels.h) read. Plain data: it compiles in a host-only
+// host and the kernels (jt_device.h, jt_kernels.h and its headers) read. Plain data: it compiles in a host-only
 // C++ translation unit (-D__HIP_PLATFORM_AMD__) as well as in HIP.
 #pragma once
 
@@ -79,7 +79,7 @@ enum : int {
     FT_NONE = 0,
     FT_ALL = 255,
     // kernel build flag, not a scene feature: the scene's light chains run inline
-    // (DScene::light_inline; jt_kernels.h light_chain), so the kernel has no light-hit steps
+    // (DScene::light_inline; jt_integrator.h light_chain), so the kernel has no light-hit steps
     FT_LINL = 8192,
     // kernel build flag: the scene has no instance light (sample_lights_pdf never queries a BVH)
     FT_NOIL = 16384

@@ -2,7 +2,8 @@
 // jt_context.h): the kernel dispatch, scene upload (the steps of jt_create), the sample queue
 // and its launches, the single-device getters. The scene's validation and host layout are in
 // jt_layout.cpp (no HIP runtime), the launch plan's integer rules in jt_plan.h, the trace kernels
-// in jt_kernels.h (instantiated by jt_kv.hip, one translation unit per configuration), the
+// in jt_kernels.h (instantiated by jt_kv.hip, one translation unit per configuration; this unit
+// sees only their declarations and the argument records, jt_launch.h), the
 // combine and chain kernels in jt_accum.hip, the multi-device context in jt_multi.hip, and the
 // denoiser's and the error estimate's entry points beside their kernels (jt_denoise.hip,
 // jt_error.hip).

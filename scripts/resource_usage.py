@@ -1,5 +1,5 @@
 """Resource usage of every production kernel instance (COUNT=0) of libjtrace_hip: VGPRs, spilled
-VGPRs, scratch bytes per lane, occupancy, per launch configuration (csrc/jt_kernels.h
+VGPRs, scratch bytes per lane, occupancy, per launch configuration (csrc/jt_launch.h
 LaunchConfig), and the scratch stores inside the kernel's loops (spill write-back executed per
 path or per query, not once per launch: the WRITE traffic the roofline records show). Compiles
 csrc/jt_kv.hip once per configuration with -Rpass-analysis and once to ISA.

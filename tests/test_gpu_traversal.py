@@ -6,7 +6,7 @@ far child. The option inverts the push order. The oracle restates the same switc
 (oracle/jt_oracle.c, intersect_scene_bvh / intersect_shape_bvh), so HIP vs oracle stays at the
 parity bar in both orders. Exact-t ties (the later-tested of two equally distant primitives wins,
 src/geometry.jl:226) resolve as in the reference's order (the near-first orders reverse the
-reference's leaf sequence and keep each leaf's order, csrc/jt_kernels.h tie_ok); only a hit the
+reference's leaf sequence and keep each leaf's order, csrc/jt_traverse.h rerun_tie); only a hit the
 slab test's rounding lets one order find and the other cull can differ: the images must meet the
 §8(c) bar against each other at the configs' full size and spp.
 """
@@ -85,7 +85,7 @@ def test_default_order_vs_reference_order_full_size(gpu, abi, lib, cornell_abi, 
     against the reference's exact far-first order (src/bvh.jl:331-341), GPU vs GPU at the configs'
     full size and spp, at the §8(c) bar: >= 99.9 % of pixels within 1e-3 relative, image mean within
     1e-4. The near-first orders resolve exact-t ties as the reference's order does (the later leaf
-    in the reference's sequence wins, csrc/jt_kernels.h tie_ok), so what remains is a hit the slab
+    in the reference's sequence wins, csrc/jt_traverse.h rerun_tie), so what remains is a hit the slab
     test's rounding lets one order find and the other cull (oracle/jt_oracle.c or_order_diff)."""
     from jtrace import trace
     sa = cornell_abi if name == "cornellbox" else scene_abi(name)
