@@ -20,6 +20,7 @@
  *                      an a-trous filter over those means; jt_get_denoised reads its result
  *   jt_get_variance    (the build's own) the per-pixel variance of the image, from the spread of
  *                      the sample streams' means; jt_get_noise its image-level relative RMS error
+ *   jt_denoise_guided  (the build's own) the a-trous filter with that variance as its colour tolerance
  *   jt_destroy / jt_last_error — lifetime and error reporting (the reference throws Julia exceptions)
  *
  * Host helpers (run on the CPU, no device needed) that restate the reference's host code
@@ -273,6 +274,17 @@ typedef struct jt_denoise_params {
     float albedo_floor;  /* lower bound of the albedo the radiance is divided by */
 } jt_denoise_params;
 
+/* Parameters of the variance-guided denoiser (jt_denoise_guided). iterations: 1..8; every other
+ * field finite, > 0, and sigma_variance^2 * variance_floor a normal float. */
+typedef struct jt_denoise_guided_params {
+    int32_t iterations;    /* a-trous iterations I; iteration i taps at a distance of 2^i pixels */
+    float sigma_variance;  /* colour tolerance in standard deviations of the two pixels' difference */
+    float sigma_normal;
+    float sigma_albedo;
+    float albedo_floor;    /* lower bound of the albedo the radiance is divided by */
+    float variance_floor;  /* lower bound of V(p) + V(q), of demodulated radiance */
+} jt_denoise_guided_params;
+
 typedef struct jt_ctx jt_ctx;
 
 /* ---- library ---------------------------------------------------------------------- */
@@ -408,7 +420,7 @@ int jt_denoise_defaults(int32_t samples, jt_denoise_params* out);
  * > 0. A multi-device context reduces image, albedo and normal as jt_get_image / jt_get_aovs do
  * and filters them on its first device. */
 int jt_denoise(jt_ctx* ctx, const jt_denoise_params* params);
-/* The result of the last jt_denoise, W*H*4. JT_ERR_STATE when none has run since the last
+/* The result of the last jt_denoise or jt_denoise_guided, W*H*4. JT_ERR_STATE when none has run since the last
  * sample was traced (or queued) or since jt_reset: a stale result is never returned. */
 int jt_get_denoised(jt_ctx* ctx, float* rgba);
 /* The same filter on the caller's host arrays (rgba W*H*4, albedo W*H*3, normal W*H*3, row-major)
@@ -419,6 +431,49 @@ int jt_get_denoised(jt_ctx* ctx, float* rgba);
  * the tracer's own buffers never hold any. */
 int jt_denoise_image(const float* rgba, const float* albedo, const float* normal, int32_t width, int32_t height,
                      const jt_denoise_params* params, int32_t device, float* out_rgba);
+
+/* The variance-guided filter: the same window and guides, but the colour tolerance of a tap is
+ * the two pixels' own variance (the error estimate below) instead of one global sigma_color, and
+ * that variance is carried through the iterations. All float32, no FMA. With c the mean radiance
+ * RGBA, v the variance of the mean RGBA as jt_get_variance returns it (v.a is ignored), a the
+ * mean albedo, n the mean normal (as accumulated):
+ *   m = max(a, albedo_floor) per channel;  d_0 = c.rgb / m;
+ *   u = v.rgb / (m * m) per channel;  V_0 = (u.x + u.y) + u.z;  sv2 = sigma_variance * sigma_variance;
+ *   for i = 0 .. iterations-1, s = 2^i, at every pixel p:
+ *     taps q = p + s (dx, dy), dx, dy in -2..2; taps outside the image are skipped;
+ *     e(p,q) = |d_i(p)-d_i(q)|^2 / (sv2 * max(V_i(p) + V_i(q), variance_floor))
+ *            + |n(p)-n(q)|^2 / sigma_normal^2 + |a(p)-a(q)|^2 / sigma_albedo^2;
+ *     w(p,q) = k[dy+2] k[dx+2] exp(-e),  k = {1/16, 1/4, 3/8, 1/4, 1/16} (the centre tap weighs 9/64);
+ *     d_{i+1}(p) = sum_q w d_i(q) / sum_q w;
+ *     V_{i+1}(p) = sum_q (w * w) V_i(q) / (sum_q w)^2;
+ *   out.rgb = d_I * m;  out.a = c.a, copied by its bits.
+ * |.|^2 is summed over the three channels, as in jt_denoise. The colour tolerance is not halved
+ * per iteration: the propagated variance shrinks it where the filter has already averaged. The
+ * weight is symmetric (V(p) + V(q)), so a pixel whose own estimate is 0 still accepts a noisy
+ * neighbour's evidence while two zero-variance pixels stay anchors; V_0 = 0 everywhere makes the
+ * filter the identity up to the c / m * m round trip.
+ * jt_denoise_guided_defaults (host only, independent of the sample count: the variance carries
+ * it): iterations 5, sigma_variance 2.0, sigma_normal 0.3, sigma_albedo 0.1, albedo_floor 0.01,
+ * variance_floor 1e-10. */
+int jt_denoise_guided_defaults(jt_denoise_guided_params* out);
+/* Filters the context's running means into the buffer jt_denoise uses; jt_get_denoised reads the
+ * result of whichever of the two ran last, and its staleness rule is unchanged. params NULL: the
+ * defaults. Traces the queued samples first and obtains the error estimate exactly as
+ * jt_get_variance does: one already valid for these samples is reused, and one computed here
+ * serves a later jt_get_variance / jt_get_noise. Image, albedo, normal, hits, the stream means,
+ * the variance and every jt_counters field stay bit for bit as they were.
+ * Errors, in this order: JT_ERR_INVALID (naming the field) for a NULL ctx, iterations outside
+ * 1..8, a field that is not finite and > 0, or a sigma_variance^2 * variance_floor that
+ * underflows; then every error of jt_get_variance: JT_ERR_UNSUPPORTED for a multi-device context
+ * (jt_create_multi), JT_ERR_STATE for a failed context, a one-stream context, no sample, or fewer
+ * than two samples. */
+int jt_denoise_guided(jt_ctx* ctx, const jt_denoise_guided_params* params);
+/* The same filter on the caller's host arrays, as jt_denoise_image with variance W*H*4 (alpha
+ * ignored). Arguments and sizes are checked before any device work; params is required.
+ * Negative or non-finite variance is the caller's responsibility. */
+int jt_denoise_guided_image(const float* rgba, const float* variance, const float* albedo, const float* normal,
+                            int32_t width, int32_t height, const jt_denoise_guided_params* params, int32_t device,
+                            float* out_rgba);
 
 /* ---- error estimate -------------------------------------------------------------------- */
 /* The per-pixel variance of the image, from the spread of the sample streams' means. A

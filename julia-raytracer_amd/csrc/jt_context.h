@@ -70,9 +70,10 @@ struct jt_ctx {
     hipEvent_t trace_done[2] = {nullptr, nullptr}, chain_done[2] = {nullptr, nullptr};
 
     // ---- denoise
-    // the denoiser (jt_denoise, jt_denoise.hip): two scratch buffers and the result, float4[W*H]
-    // each, allocated by the first jt_denoise and kept across jt_reset. A multi-device context
-    // filters the reduced host arrays on device 0 and keeps the result on the host instead
+    // the denoiser (jt_denoise, jt_denoise_guided; jt_denoise.hip): two scratch buffers and the
+    // result, float4[W*H] each, allocated by the first call of either and kept across jt_reset;
+    // the result is that of the last to run. A multi-device context (jt_denoise only) filters the
+    // reduced host arrays on device 0 and keeps the result on the host instead
     float4* dn[3] = {nullptr, nullptr, nullptr};
     bool denoised = false;  // the result is the filter of the current running means
 

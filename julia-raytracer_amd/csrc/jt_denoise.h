@@ -18,4 +18,12 @@ int denoise_check_size(int32_t width, int32_t height);
 hipError_t denoise_launch(hipStream_t stream, const float4* image, const float4* albedo, const float4* normal, int width,
                           int height, const jt_denoise_params& p, float4* ping, float4* pong, float4* out);
 
+// The variance-guided filter (jt_denoise_guided): the same contract, with `variance` the
+// variance of the mean per channel as jt_get_variance returns it (w ignored). Also refuses a
+// sigma_variance^2 * variance_floor that underflows: every tap divides by at least that.
+int denoise_guided_check_params(const jt_denoise_guided_params* p);
+hipError_t denoise_guided_launch(hipStream_t stream, const float4* image, const float4* variance, const float4* albedo,
+                                 const float4* normal, int width, int height, const jt_denoise_guided_params& p,
+                                 float4* ping, float4* pong, float4* out);
+
 }  // namespace jt

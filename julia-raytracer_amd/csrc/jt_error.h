@@ -1,5 +1,5 @@
-// jt_error.h — the per-pixel error estimate's launch; the kernel and the context's half
-// (jt_get_variance, jt_get_noise) are in jt_error.hip. Not part of the ABI.
+// jt_error.h — the per-pixel error estimate's launch and its context entry; the kernel and the
+// context's half (jt_get_variance, jt_get_noise) are in jt_error.hip. Not part of the ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -34,3 +34,15 @@ inline int error_blocks(int tiles) { return (int)(((long long)tiles * 64 + ERR_B
 hipError_t error_launch(hipStream_t stream, const DError& E);
 
 }  // namespace jt
+
+struct jt_ctx;
+
+namespace jtc {
+
+// The error estimate of a context's current samples, into jt_ctx::err_var / err_noise: every check
+// of jt_get_variance (include/jtrace.h) in its order, the flush, then one launch unless the
+// result is already valid for these samples. Its readers: jt_get_variance, jt_get_noise and
+// jt_denoise_guided (jt_denoise.hip).
+int estimate_error(jt_ctx* c);
+
+}  // namespace jtc

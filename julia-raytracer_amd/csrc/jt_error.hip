@@ -83,12 +83,11 @@ hipError_t error_launch(hipStream_t stream, const DError& E) {
 // ---- the context's half (jt_context.h)
 using namespace jtc;
 
-namespace {
 // The error estimate of the current samples (include/jtrace.h jt_get_variance): checks, the flush,
 // then one launch of error_kernel over the stream means the last combine read, unless the
 // result of these samples is already there. Neither counted in jt_counters nor touching an
 // accumulator or a stream mean.
-int estimate_error(jt_ctx* c) {
+int jtc::estimate_error(jt_ctx* c) {
     if (c->multi)
         return jt::fail(JT_ERR_UNSUPPORTED,
                         "the error estimate is not available on a multi-device context (jt_create_multi): "
@@ -146,7 +145,6 @@ int estimate_error(jt_ctx* c) {
     c->err_valid = true;
     return JT_OK;
 }
-}  // namespace
 
 extern "C" {
 

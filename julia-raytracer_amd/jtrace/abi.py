@@ -140,6 +140,14 @@ class jt_denoise_params(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class jt_denoise_guided_params(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("sigma_variance", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_albedo", C.c_float), ("albedo_floor", C.c_float), ("variance_floor", C.c_float)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 assert C.sizeof(jt_bvh_node) == 32
 
 
@@ -287,6 +295,10 @@ def _declare(lib):
     lib.jt_get_denoised.argtypes = [C.c_void_p, f32p]
     lib.jt_denoise_image.argtypes = [f32p, f32p, f32p, C.c_int32, C.c_int32, C.POINTER(jt_denoise_params),
                                      C.c_int32, f32p]
+    lib.jt_denoise_guided_defaults.argtypes = [C.POINTER(jt_denoise_guided_params)]
+    lib.jt_denoise_guided.argtypes = [C.c_void_p, C.POINTER(jt_denoise_guided_params)]
+    lib.jt_denoise_guided_image.argtypes = [f32p, f32p, f32p, f32p, C.c_int32, C.c_int32,
+                                            C.POINTER(jt_denoise_guided_params), C.c_int32, f32p]
     lib.jt_get_variance.argtypes = [C.c_void_p, f32p]
     lib.jt_get_noise.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     lib.jt_reset.argtypes = [C.c_void_p]
@@ -306,7 +318,7 @@ EXPORTED_SYMBOLS = [
     "jt_trace_samples", "jt_trace_range", "jt_get_streams", "jt_get_samples", "jt_get_size", "jt_get_image",
     "jt_get_aovs", "jt_get_counters", "jt_reset", "jt_get_device_buffers", "jt_set_counters", "jt_describe", "jt_synchronize",
     "jt_destroy", "jt_denoise_defaults", "jt_denoise", "jt_get_denoised", "jt_denoise_image",
-    "jt_get_variance", "jt_get_noise",
+    "jt_get_variance", "jt_get_noise", "jt_denoise_guided_defaults", "jt_denoise_guided", "jt_denoise_guided_image",
 ]
 
 

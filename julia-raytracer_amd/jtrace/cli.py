@@ -5,8 +5,9 @@ Extensions beyond the reference (all optional): --seed (RNG seed), --width/--hei
 image size, camera aspect := W/H), --device, --devices N (one context over GPUs 0..N-1:
 jt_create_multi), --missing (drop|error for incomplete scenes), --traversal (reference|near|wide|auto:
 the BVH traversal, include/jtrace.h jt_traversal), --noise-target / --noise-interval (stop at an
-estimated relative RMS error, jt_get_noise) and --error-output (the per-pixel standard error as a
-second image, jt_get_variance).
+estimated relative RMS error, jt_get_noise), --error-output (the per-pixel standard error as a
+second image, jt_get_variance) and --denoise-mode (plain|variance: with --denoise true, the filter of
+jt_denoise or the variance-guided one of jt_denoise_guided).
 """
 from __future__ import annotations
 
@@ -20,6 +21,8 @@ SAMPLER_TYPES = ["path", "naive"]
 # by the library (jt_describe reports which). "reference" is the reference's far-first order (src/bvh.jl:331-341); all differ only
 # where two hits tie at exactly equal t or a box is culled by the slab test's rounding.
 DEFAULT_TRAVERSAL = "auto"
+# --denoise-mode: which filter --denoise true runs (read only then)
+DENOISE_MODES = ["plain", "variance"]
 
 
 def _bool(s: str) -> bool:  # ArgParse arg_type = Bool parses "true"/"false"
@@ -72,6 +75,10 @@ def _parser() -> argparse.ArgumentParser:
     p.add_argument("--error-output", type=str, default="",
                    help="also save the per-pixel standard error, sqrt of jt_get_variance, to this file "
                         "(extension; needs --batch >= 2)")
+    p.add_argument("--denoise-mode", choices=DENOISE_MODES, default="plain",
+                   help="with --denoise true: plain (jt_denoise, one colour sigma from the sample count) or "
+                        "variance (jt_denoise_guided, the per-pixel variance of jt_get_variance as the colour "
+                        "tolerance; extension; needs --batch >= 2)")
     return p
 
 
@@ -81,7 +88,8 @@ def _check_error_flags(parser: argparse.ArgumentParser, ns) -> None:
         parser.error(f"--noise-target must be >= 0 (0: off), got {ns.noise_target}")
     if ns.noise_interval < 1:
         parser.error(f"--noise-interval must be at least 1, got {ns.noise_interval}")
-    for flag, used in (("--noise-target", ns.noise_target > 0), ("--error-output", ns.error_output != "")):
+    for flag, used in (("--noise-target", ns.noise_target > 0), ("--error-output", ns.error_output != ""),
+                       ("--denoise-mode variance", ns.denoise and ns.denoise_mode == "variance")):
         if used and ns.batch < 2:
             parser.error(f"{flag} needs two sample streams per pixel: --batch {ns.batch} renders with one; "
                          "pass --batch 2 or more")
@@ -120,6 +128,7 @@ class Params:
     noise_target: float = 0.0
     noise_interval: int = 16
     error_output: str = ""
+    denoise_mode: str = "plain"
 
 
 def params_from_dict(d: dict) -> Params:

@@ -86,10 +86,13 @@ def run(params: Params, out=print) -> dict:
     render_s = time.perf_counter() - sampling_start
     out(f"rendered in {format_seconds(render_s)} ({render_s:.3f}s)")
     samples_traced = state.samples
-    if params.denoise:  # the a-trous filter over the albedo and normal means (jt_denoise)
+    # the a-trous filter over the albedo and normal means: jt_denoise, or with --denoise-mode
+    # variance jt_denoise_guided, whose colour tolerance is the per-pixel variance
+    denoise_mode = getattr(params, "denoise_mode", "plain") or "plain"
+    if params.denoise:
         out("denoising...")
         t0 = time.perf_counter()
-        image = state.denoise()
+        image = state.denoise_guided() if denoise_mode == "variance" else state.denoise()
         out(f"denoised in {format_seconds(time.perf_counter() - t0)}")
     out("saving image...")
     if not params.denoise:
@@ -110,6 +113,7 @@ def run(params: Params, out=print) -> dict:
     state.close()
     if params.denoise:
         result["denoised"] = True
+        result["denoise_mode"] = denoise_mode
     return result
 
 

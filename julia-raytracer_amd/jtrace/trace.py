@@ -8,6 +8,9 @@
     state.denoise() / denoise_image / denoise_defaults (the build's own) -> jt_denoise, jt_get_denoised,
                                                        jt_denoise_image, jt_denoise_defaults
     state.variance() / state.noise() (the build's own) -> jt_get_variance, jt_get_noise
+    state.denoise_guided() / denoise_guided_image / denoise_guided_defaults (the build's own)
+                                                       -> jt_denoise_guided, jt_denoise_guided_image,
+                                                       jt_denoise_guided_defaults
 
 There is no CPU fallback anywhere in this module: every call goes through libjtrace_hip.so.
 """
@@ -159,6 +162,19 @@ class TraceState:
         abi.check(self.lib, self.lib.jt_get_denoised(self.handle, out.ctypes.data_as(abi.f32p)))
         return out
 
+    def denoise_guided(self, params: abi.jt_denoise_guided_params | None = None, **overrides) -> np.ndarray:
+        """jt_denoise_guided then jt_get_denoised: the (H, W, 4) float32 variance-guided a-trous
+        filter of the running means, its colour tolerance the per-pixel variance of
+        jt_get_variance (include/jtrace.h). Needs k > 1 streams and two samples. params None: the
+        defaults; overrides replace single fields (iterations, sigma_variance, ...) of either."""
+        if overrides and params is None:
+            params = denoise_guided_defaults(self.lib)
+        params = _with_overrides(params, overrides)
+        abi.check(self.lib, self.lib.jt_denoise_guided(self.handle, None if params is None else C.byref(params)))
+        out = np.empty((self.height, self.width, 4), np.float32)
+        abi.check(self.lib, self.lib.jt_get_denoised(self.handle, out.ctypes.data_as(abi.f32p)))
+        return out
+
     def variance(self) -> np.ndarray:
         """jt_get_variance: the (H, W, 4) float32 variance of the image per channel (of the mean,
         not of one sample), from the spread of the sample streams' means. Needs k > 1 streams
@@ -232,8 +248,8 @@ def get_image(state: TraceState) -> np.ndarray:
 def _with_overrides(params, overrides):
     if not overrides:
         return params
-    p = abi.jt_denoise_params.from_buffer_copy(params)
-    names = [name for name, _ in abi.jt_denoise_params._fields_]
+    p = type(params).from_buffer_copy(params)  # jt_denoise_params or jt_denoise_guided_params
+    names = [name for name, _ in p._fields_]
     for name, value in overrides.items():
         if name not in names:
             raise TypeError(f"unknown denoise parameter {name!r} (one of {', '.join(names)})")
@@ -265,4 +281,36 @@ def denoise_image(rgba, albedo, normal, device: int = 0, params: abi.jt_denoise_
     abi.check(lib, lib.jt_denoise_image(rgba.ctypes.data_as(abi.f32p), albedo.ctypes.data_as(abi.f32p),
                                         normal.ctypes.data_as(abi.f32p), rgba.shape[1], rgba.shape[0], C.byref(p),
                                         int(device), out.ctypes.data_as(abi.f32p)))
+    return out
+
+
+def denoise_guided_defaults(lib=None) -> abi.jt_denoise_guided_params:
+    """jt_denoise_guided_defaults: the variance-guided denoiser's parameters (the same for every
+    sample count: the variance carries it)."""
+    lib = lib or abi.load_library()
+    p = abi.jt_denoise_guided_params()
+    abi.check(lib, lib.jt_denoise_guided_defaults(C.byref(p)))
+    return p
+
+
+def denoise_guided_image(rgba, variance, albedo, normal, device: int = 0,
+                         params: abi.jt_denoise_guided_params | None = None, lib=None, **overrides) -> np.ndarray:
+    """jt_denoise_guided_image: the variance-guided denoiser on host arrays (H, W, 4), (H, W, 4),
+    (H, W, 3), (H, W, 3) -> (H, W, 4) float32, on HIP device `device`; variance as
+    TraceState.variance() returns it. params None: the defaults; overrides replace single fields."""
+    lib = lib or abi.load_library()
+    rgba = np.ascontiguousarray(rgba, np.float32)
+    variance = np.ascontiguousarray(variance, np.float32)
+    albedo = np.ascontiguousarray(albedo, np.float32)
+    normal = np.ascontiguousarray(normal, np.float32)
+    if (rgba.ndim != 3 or rgba.shape[2] != 4 or variance.shape != rgba.shape or albedo.shape != rgba.shape[:2] + (3,)
+            or normal.shape != albedo.shape):
+        raise ValueError(f"expected (H, W, 4), (H, W, 4), (H, W, 3), (H, W, 3) arrays, got {rgba.shape}, "
+                         f"{variance.shape}, {albedo.shape}, {normal.shape}")
+    p = _with_overrides(params if params is not None else denoise_guided_defaults(lib), overrides)
+    out = np.empty_like(rgba)
+    abi.check(lib, lib.jt_denoise_guided_image(rgba.ctypes.data_as(abi.f32p), variance.ctypes.data_as(abi.f32p),
+                                               albedo.ctypes.data_as(abi.f32p), normal.ctypes.data_as(abi.f32p),
+                                               rgba.shape[1], rgba.shape[0], C.byref(p), int(device),
+                                               out.ctypes.data_as(abi.f32p)))
     return out

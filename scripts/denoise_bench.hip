@@ -1,8 +1,10 @@
-// denoise_bench.hip — device time of the denoiser's launches (jt::denoise_launch,
-// julia-raytracer_amd/csrc/jt_denoise.hip) at a frame size a user renders, HIP events around the
-// launches, the iteration counts 1..I interleaved round by round in one process. The time of
-// iteration i is read as T(i + 1 iterations) - T(i iterations). Data are seeded noise over
-// piecewise constant guides: the filter's work per pixel does not depend on the values.
+// denoise_bench.hip — device time of the denoiser's launches (jt::denoise_launch and
+// jt::denoise_guided_launch, julia-raytracer_amd/csrc/jt_denoise.hip) at a frame size a user
+// renders, HIP events around the launches, the two filters and the iteration counts 1..I
+// interleaved round by round in one process. The time of iteration i is read as
+// T(i + 1 iterations) - T(i iterations). Data are seeded noise over piecewise constant guides, the
+// variance that of a 30 % relative standard error: the filters' work per pixel does not depend
+// on the values.
 //
 //   make -C julia-raytracer_amd denoise-bench && julia-raytracer_amd/build/denoise_bench [W H rounds]
 #include <hip/hip_runtime.h>
@@ -34,7 +36,9 @@ int main(int argc, char** argv) {
     jt_denoise_defaults(16, &p);
     const int I = p.iterations;
     const size_t np = (size_t)W * H;
-    std::vector<float4> host(np * 3);
+    jt_denoise_guided_params g;
+    jt_denoise_guided_defaults(&g);
+    std::vector<float4> host(np * 4);
     unsigned s = 12345u;
     auto rnd = [&] { return (float)((s = s * 1664525u + 1013904223u) >> 8) * (1.0f / 16777216.0f); };
     for (size_t k = 0; k < np; k++) {
@@ -43,30 +47,42 @@ int main(int argc, char** argv) {
         host[np + k] = make_float4(a, 0.5f * a, 1.0f - a, 0.0f);
         host[2 * np + k] = make_float4(region == 0, region == 1, region == 2, 0.0f);
         host[k] = make_float4(a * (0.5f + rnd()), 0.5f * a * (0.5f + rnd()), (1.0f - a) * (0.5f + rnd()), 1.0f);
+        const float4 c = host[k];
+        host[3 * np + k] = make_float4(0.09f * c.x * c.x, 0.09f * c.y * c.y, 0.09f * c.z * c.z, 0.0f);
     }
     float4* d = nullptr;
-    CHECK(hipMalloc((void**)&d, np * 16 * 6));
-    CHECK(hipMemcpy(d, host.data(), np * 48, hipMemcpyHostToDevice));
+    // image, albedo, normal, variance, ping, pong, out
+    CHECK(hipMalloc((void**)&d, np * 16 * 7));
+    CHECK(hipMemcpy(d, host.data(), np * 64, hipMemcpyHostToDevice));
     hipStream_t st;
     hipEvent_t e0, e1;
     CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
     CHECK(hipEventCreate(&e0));
     CHECK(hipEventCreate(&e1));
-    std::vector<std::vector<float>> ms(I + 1);
+    std::vector<std::vector<float>> ms(I + 1), gms(I + 1);
     for (int r = -3; r < rounds; r++) {  // three warm-up rounds
         for (int it = 1; it <= I; it++) {
             jt_denoise_params q = p;
             q.iterations = it;
             CHECK(hipEventRecord(e0, st));
-            CHECK(jt::denoise_launch(st, d, d + np, d + 2 * np, W, H, q, d + 3 * np, d + 4 * np, d + 5 * np));
+            CHECK(jt::denoise_launch(st, d, d + np, d + 2 * np, W, H, q, d + 4 * np, d + 5 * np, d + 6 * np));
             CHECK(hipEventRecord(e1, st));
             CHECK(hipEventSynchronize(e1));
             float t = 0;
             CHECK(hipEventElapsedTime(&t, e0, e1));
             if (r >= 0) ms[it].push_back(t);
+            jt_denoise_guided_params gq = g;
+            gq.iterations = it;
+            CHECK(hipEventRecord(e0, st));
+            CHECK(jt::denoise_guided_launch(st, d, d + 3 * np, d + np, d + 2 * np, W, H, gq, d + 4 * np, d + 5 * np,
+                                            d + 6 * np));
+            CHECK(hipEventRecord(e1, st));
+            CHECK(hipEventSynchronize(e1));
+            CHECK(hipEventElapsedTime(&t, e0, e1));
+            if (r >= 0) gms[it].push_back(t);
         }
     }
-    std::printf("denoise %dx%d, defaults for 16 spp, %d rounds, iteration counts interleaved\n", W, H, rounds);
+    std::printf("denoise %dx%d, defaults for 16 spp, %d rounds, filters and iteration counts interleaved\n", W, H, rounds);
     const double compulsory = 64.0 * (double)np;  // d, albedo, normal read, d written: 64 B per pixel
     double prev = 0;
     for (int it = 1; it <= I; it++) {
@@ -79,5 +95,18 @@ int main(int argc, char** argv) {
         prev = med;
     }
     std::printf("one default denoise (%d iterations): median %.4f ms\n", I, prev);
+    const double plain = prev;
+    prev = 0;
+    for (int it = 1; it <= I; it++) {
+        std::sort(gms[it].begin(), gms[it].end());
+        const double med = gms[it][gms[it].size() / 2], mn = gms[it].front();
+        const double dt = med - prev;
+        std::printf("guided iterations=%d  median %.4f ms  min %.4f ms  | step %2d (+demodulate at 1): %.4f ms, "
+                    "compulsory %.1f MB = %.2f TB/s\n",
+                    it, med, mn, 1 << (it - 1), dt, compulsory / 1e6, compulsory / (dt * 1e-3) / 1e12);
+        prev = med;
+    }
+    std::printf("one default guided denoise (%d iterations): median %.4f ms, %.3f x the plain filter\n", I, prev,
+                prev / plain);
     return 0;
 }
