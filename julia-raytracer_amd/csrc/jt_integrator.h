@@ -315,6 +315,7 @@ __device__ __forceinline__ bool light_chain(const DScene& S, const DParams& P, P
     // DINV_ONCE the first query's 1/d and push mask stay in the query state for the later ones
     // (with instance transforms a query may leave its instance's mask in T.negmask: not that one)
     constexpr bool DINV_ONCE = chain_dinv_once<WIDE, OVF, NCACHE, F>();
+    constexpr int PB = push_bit(node_baked<OVF, NCACHE, WIDE, F>());
     const auto dinv = [&] { T.wdinv = V3(jl_rcp(st.d.x), jl_rcp(st.d.y), jl_rcp(st.d.z)); };  // ray_dinv (src/bvh.jl:322), no guard
     // one intersect_instance_bvh of the current light
     const auto query = [&] {
@@ -322,21 +323,21 @@ __device__ __forceinline__ bool light_chain(const DScene& S, const DParams& P, P
         const int inst = S.lights[st.li].instance;
         if (LEAF) {
             if (!DINV_ONCE) dinv();
-            const int negmask = DINV_ONCE && !(F & FT_XFORM) ? T.negmask : neg_mask(st.d, S.order_flip);
+            const int negmask = DINV_ONCE && !(F & FT_XFORM) ? T.negmask : neg_mask(st.d, S.order_flip | PB);
             inst_leaf_query<COUNT, F>(S, T, st.o, st.d, T.wdinv, negmask, inst, cnt);
             while (T.nprim > 0) prim_step<COUNT, F>(S, T, cnt);
         } else {
-            query_start<WIDE>(S, T, st.o, st.d, inst, stack);
+            query_start<WIDE>(S, T, st.o, st.d, inst, stack, 0, PB);
             do {
                 node_step_any<WIDE, RING, OVF, COUNT, NCACHE, F>(S, T, stack, pixel, cnt);  // instance + its one-leaf root
                 while (T.nprim > 0) prim_step<COUNT, F>(S, T, cnt);
-            } while (RERUN_LOOP && rerun_tie<WIDE>(S, T, st.o, st.d, inst, stack));
+            } while (RERUN_LOOP && rerun_tie<WIDE>(S, T, st.o, st.d, inst, stack, PB));
         }
     };
     if (TAIL) {
         if (DINV_ONCE) {
             dinv();
-            if (!(F & FT_XFORM)) T.negmask = neg_mask(st.d, S.order_flip);
+            if (!(F & FT_XFORM)) T.negmask = neg_mask(st.d, S.order_flip | PB);
         }
         for (;;) {
             // one light's chain: a lane stays while its query hits; then the chain's end, once for

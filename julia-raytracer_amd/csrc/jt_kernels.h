@@ -261,6 +261,7 @@ __device__ __forceinline__ void trace_body_items(const DScene& S0, const DParams
     const DScene& S = S0;
     const DParams& P = P0;
     static_assert(lane_lds(F), "the per-lane item body keeps the lane's sample index in LDS");
+    constexpr int PB = push_bit(node_baked<OVF, NCACHE, WIDE, F>());  // the push mask's bit of a baking kernel
     const int lane = threadIdx.x & 63;
     const int oslot = (int)blockIdx.x * BLOCK + (int)threadIdx.x;  // the lane's HBM stack-overflow area
     if constexpr ((F & (FT_TEX | FT_ENV)) != 0) {  // the texel-decode LUTs into LDS (tex_lut)
@@ -401,7 +402,7 @@ __device__ __forceinline__ void trace_body_items(const DScene& S0, const DParams
             if (!ft_none(F)) acc[12 * BLOCK] = stream_weight(P, sample);
             const DParams& P = karg_params<karg_params_on<SAMPLER, F>()>(P0);
             start_path<F>(P, pixel % P.width, pixel / P.width, pixel, sample, st);
-            query_start<WIDE>(S, T, st.o, st.d, -1, stack);
+            query_start<WIDE>(S, T, st.o, st.d, -1, stack, 0, PB);
             if (!WC) lds_count(1, true);
             if constexpr (item_first_pop<WIDE, F>()) {
 #pragma unroll
@@ -437,7 +438,7 @@ __device__ __forceinline__ void trace_body_items(const DScene& S0, const DParams
                 const int nl = lane_count(__builtin_amdgcn_ballot_w64(wantl));
                 if (nl > 0 && (nl >= P.light_lanes || nb == 0)) {
                     bool c_lq = false, c_ray = false;
-                    if (wantl && rerun_tie<WIDE>(S, T, st.o, st.d, S.lights[st.li].instance, stack)) {
+                    if (wantl && rerun_tie<WIDE>(S, T, st.o, st.d, S.lights[st.li].instance, stack, PB)) {
                         // an exact-t tie: the query runs again in the reference's order
                     } else if (wantl) {
                         if (light_hit<F>(S, P, st, query_hit(T))) {
@@ -445,11 +446,11 @@ __device__ __forceinline__ void trace_body_items(const DScene& S0, const DParams
                         } else if (st.phase == PH_LIGHT) {
                             if (WC) c_lq = true;
                             else lds_count(2, true);
-                            query_start<WIDE>(S, T, st.o, st.d, S.lights[st.li].instance, stack);
+                            query_start<WIDE>(S, T, st.o, st.d, S.lights[st.li].instance, stack, 0, PB);
                         } else {
                             if (WC) c_ray = true;
                             else lds_count(1, true);
-                            query_start<WIDE>(S, T, st.o, st.d, -1, stack);
+                            query_start<WIDE>(S, T, st.o, st.d, -1, stack, 0, PB);
                         }
                     }
                     if (WC) {
@@ -519,7 +520,7 @@ __device__ __forceinline__ void trace_body_items(const DScene& S0, const DParams
             const bool tie = query_done<WIDE>(T) && (T.nh & (TIE_SEEN | REF_RERUN)) == TIE_SEEN &&
                              !(LSTEP && st.phase == PH_FINISH);
             if (S.order_flip && __builtin_amdgcn_ballot_w64(tie))
-                if (tie) rerun_tie<WIDE>(S, T, st.o, st.d, SAMPLER == 1 && !LINL && st.phase == PH_LIGHT ? S.lights[st.li].instance : -1, stack);
+                if (tie) rerun_tie<WIDE>(S, T, st.o, st.d, SAMPLER == 1 && !LINL && st.phase == PH_LIGHT ? S.lights[st.li].instance : -1, stack, PB);
         }
         bool c_path = false, c_lq = false, c_ray = false;
         unsigned n_inl = 0;
@@ -603,7 +604,7 @@ __device__ __forceinline__ void trace_body_items(const DScene& S0, const DParams
                 if (SAMPLER == 1 && !LINL && st.phase == PH_LIGHT) {
                     if (WC) c_lq = true;
                     else lds_count(2, true);
-                    query_start<WIDE>(S, T, st.o, st.d, S.lights[st.li].instance, stack);
+                    query_start<WIDE>(S, T, st.o, st.d, S.lights[st.li].instance, stack, 0, PB);
                 } else {
                     if (WC) c_ray = true;
                     else lds_count(1, true);
@@ -612,8 +613,8 @@ __device__ __forceinline__ void trace_body_items(const DScene& S0, const DParams
                     // keep the chain's 1/d: st.d has not changed since. A wave-uniform choice, so
                     // only one of the two forms executes.
                     if (SAMPLER == 1 && chain_dinv_once<WIDE, OVF, NCACHE, F>() && __builtin_amdgcn_ballot_w64(!chained) == 0)
-                        query_restart<F>(S, T, st.o, st.d, stack);
-                    else query_start<WIDE>(S, T, st.o, st.d, -1, stack);
+                        query_restart<F>(S, T, st.o, st.d, stack, PB);
+                    else query_start<WIDE>(S, T, st.o, st.d, -1, stack, 0, PB);
                 }
                 // the query's first pop (TLAS root, or the light instance and its BLAS root) here,
                 // where most of the wave's lanes take part, rather than in a sparser traversal step
@@ -698,6 +699,23 @@ __device__ __forceinline__ DScene blob_scene(const DScene& S, const uint4* blob)
     return L;
 }
 
+// The bake pass of the LDS-mode kernels whose node step runs on the baked form (node_baked,
+// jt_traverse.h; jt_push.h): every node of the workgroup's LDS copy gets its two words rewritten,
+// once per launch, between two barriers. The host's bytes (hs.nodes, the blob in HBM) are not
+// touched. The nodes are the blob's first array, the wide records follow (JT_SCENE_ARRAYS): their
+// count is the gap, two 16-B units per node (an empty array keeps one unit: no node). The TLAS
+// nodes come first (layout_scene), so the index gives the level.
+__device__ __forceinline__ void bake_nodes(const DScene& S, uint4* blob) {
+    uint4* const nodes = blob + S.o_nodes;
+    const int nnodes = (S.o_wnodes - S.o_nodes) >> 1;
+    for (int k = threadIdx.x; k < nnodes; k += BLOCK) {
+        uint4& b = nodes[2 * k + 1];  // DNode::b: z the start word, w the meta word
+        const BakedNode bn = bake_node(b.w, (int)b.z, k < S.tlas_nnodes ? T_TLAS : T_BLAS);
+        b.z = bn.e0;
+        b.w = bn.meta;
+    }
+}
+
 // HBM mode: the scene is read from global memory (L2/MALL-resident); stack in static LDS.
 template <int SAMPLER, int RING, bool OVF, int COUNT, int F, bool WIDE>
 __global__ __launch_bounds__(BLOCK) JT_WAVES_PER_EU void trace_kernel(DScene S, DParams P, int s_begin, int s_end, DAccum A) {
@@ -715,6 +733,10 @@ __global__ __launch_bounds__(BLOCK) JT_WAVES_PER_EU_F(F) void trace_kernel_lds(D
     uint4* blob = dyn_lds + lds_stack_bytes(OVF, RING, S.stack_need) / 16;
     for (int k = threadIdx.x; k < S.blob_n16; k += BLOCK) blob[k] = S.blob[k];
     __syncthreads();
+    if constexpr (node_baked<OVF, false, WIDE, F>()) {
+        bake_nodes(S, blob);
+        __syncthreads();
+    }
     const DScene L = blob_scene(S, blob);
     trace_body_items<SAMPLER, RING, OVF, COUNT, F, false, WIDE>(L, P, s_begin, s_end, A, reinterpret_cast<int*>(dyn_lds) + threadIdx.x);
 }

@@ -1,5 +1,6 @@
 // The stack entries one binary node step pushes, as an integer function of the node: plain C++
-// (no HIP runtime), shared by jtk::node_step and the host check (tests/push_check.cpp).
+// (no HIP runtime), shared by jtk::node_step and the host checks (tests/push_check.cpp,
+// tests/push_baked_check.cpp). push_plan is the definition; the baked form below restates it.
 //
 // An internal node and a TLAS leaf both push a short run of entries whose indices are affine in
 // the slot number j:
@@ -56,6 +57,74 @@ JT_PUSH_HD PushPlan push_plan(unsigned meta, int start, unsigned type, bool blas
         const int k = j < last ? j : last;
         p.slot[j] = sp + k;
         p.value[j] = e0 + (unsigned)(p.step * k);  // = tag | (first + step*k): the index stays below 2^24
+    }
+    return p;
+}
+
+// The baked node form. Everything push_plan derives from (meta, start, level) is a constant of the
+// node, so a kernel that stages the nodes itself (trace_kernel_lds, jt_kernels.h) rewrites each
+// node's two words once per launch and its node step runs push_plan_baked on them:
+//   word z (e0): the stack entry of slot order 0, ready to store
+//       internal node   level << 30 | SNAP_NONE | start
+//       TLAS leaf       T_INST << 30 | SNAP_NONE | start
+//       BLAS leaf       start, unchanged (the leaf cursor's primitive record)
+//   word w: bits 0-15 the count, unchanged; 16-17 the axis whose push-mask bit reverses the run
+//       (a leaf: BAKE_AXIS_SET); 24-26 npush (2 / the count / 0); bit 27 a BLAS leaf; 28-29
+//       last = max(npush, 1) - 1; bit 30 min(1, last)
+// With nlast = (the mask's bit of the axis) ? last : 0, entry j is e0 + |nlast - min(j, last)| in
+// slot sp + min(j, last): the run start+1, start or start, start+1 of an internal node,
+// start+num-1 .. start of a TLAS leaf — whose axis names bit 3 of the mask, BAKE_MASK_BIT, which
+// the baking kernels keep set in every query's push mask, so a leaf needs no arm of its own. The
+// same entries in the same slots as push_plan for every node (a TLAS leaf without instances, which
+// pushes nothing, differs in the value of its dead write to slot sp); tests/push_baked_check.cpp
+// enumerates both. `start` is e0's low 24 bits, the count w's low 16.
+constexpr unsigned BAKE_AXIS_SET = 3u;  // the axis field of a leaf: reads BAKE_MASK_BIT
+constexpr int BAKE_MASK_BIT = 8;        // set in the push mask of every query of a baking kernel
+constexpr unsigned BAKE_LEAF = 1u << 27;
+
+struct BakedNode {
+    unsigned e0, meta;  // the node's words z and w
+};
+JT_PUSH_HD BakedNode bake_node(unsigned meta, int start, unsigned level) {
+    const bool internal = (meta >> 24) != 0;
+    const bool blas = level != 0u;  // T_BLAS, against T_TLAS = 0
+    const unsigned num = meta & 0xffffu;
+    const unsigned tag = (internal ? level << 30 : PUSH_T_INST << 30) | PUSH_SNAP_NONE;
+    // (a TLAS leaf holds at most PUSH_SLOTS instances: the host layout rejects larger ones)
+    const unsigned npush = internal ? 2u : blas ? 0u : (num < (unsigned)PUSH_SLOTS ? num : (unsigned)PUSH_SLOTS);
+    const unsigned last = (npush > 1u ? npush : 1u) - 1u;
+    BakedNode b;
+    b.e0 = internal || !blas ? tag | (unsigned)start : (unsigned)start;
+    b.meta = num | (internal ? (meta >> 16) & 3u : BAKE_AXIS_SET) << 16 | npush << 24 | (!internal && blas ? BAKE_LEAF : 0u) |
+             last << 28 | (last ? 1u : 0u) << 30;
+    return b;
+}
+// c + |a - b|: one instruction on the device (the compiler does not form it from the C++ below)
+JT_PUSH_HD unsigned add_absdiff(unsigned a, unsigned b, unsigned c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    unsigned r;
+    __asm__("v_sad_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+#else
+    return c + (a > b ? a - b : b - a);
+#endif
+}
+// The plan of a baked node: npush, slot, value and leaf as push_plan's; first, step and tag are
+// folded into e0 and stay zero. negmask carries BAKE_MASK_BIT.
+JT_PUSH_HD PushPlan push_plan_baked(unsigned e0, unsigned meta, int negmask, int sp) {
+    PushPlan p;
+    p.npush = (int)((meta >> 24) & 7u);
+    p.first = 0;
+    p.step = 0;
+    p.tag = 0u;
+    p.leaf = (meta & BAKE_LEAF) != 0;
+    const unsigned neg = ((unsigned)negmask >> ((meta >> 16) & 3u)) & 1u;
+    const unsigned last = (meta >> 28) & 3u;
+    const unsigned nlast = last * neg;  // neg ? last : 0
+    for (int j = 0; j < PUSH_SLOTS; j++) {
+        const unsigned k = j == 1 ? (meta >> 30) & 1u : (unsigned)j < last ? (unsigned)j : last;  // min(j, last)
+        p.slot[j] = sp + (int)k;
+        p.value[j] = j == 0 ? e0 + nlast : add_absdiff(nlast, k, e0);
     }
     return p;
 }

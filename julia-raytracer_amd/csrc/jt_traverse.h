@@ -71,21 +71,44 @@ struct Trav {
 #endif
 constexpr int TIE_SEEN = 1 << 8, REF_RERUN = 1 << 9, NH_COUNT = 63;
 // the child-order flip of the lane's current query: near-first, unless it is a tie's re-run
-__device__ __forceinline__ int query_flip(const DScene& S, const Trav& T) { return (T.nh & REF_RERUN) ? 0 : S.order_flip; }
+// (pb: push_bit of the kernel, below)
+__device__ __forceinline__ int query_flip(const DScene& S, const Trav& T, int pb = 0) {
+    return ((T.nh & REF_RERUN) ? 0 : S.order_flip) | pb;
+}
 // a hit accepted at t (t <= tmax): count it (child pre-test snapshots) and note an exact-t tie
 __device__ __forceinline__ void hit_count(Trav& T, float t) {
     T.nh = (T.nh + ((T.nh & NH_COUNT) < NH_COUNT ? 1 : 0)) | (JT_TIE_RERUN && t == T.tmax ? TIE_SEEN : 0);
 }
 
+// The baked node form (jt_push.h): the LDS-mode FT_NONE kernels whose node step takes the
+// straight-line push (binary, fixed stack: configurations 0 and 7) rewrite the nodes of their LDS
+// copy once per launch (bake_nodes, jt_kernels.h) and step on push_plan_baked. The FT_ALL kernel of
+// configuration 1 keeps push_plan: measured even to -0.2 % with the baked step.
+// Every query of a baking kernel keeps BAKE_MASK_BIT set in its push mask: push_bit, folded into
+// the constant neg_mask XORs in wherever a mask is made (the `pb` arguments below; 0 in every other
+// kernel, whose code is unchanged).
+// 0: every kernel keeps push_plan on the host's words (A/B runs).
+#ifndef JT_NODE_BAKE
+#define JT_NODE_BAKE 1
+#endif
+#ifndef JT_NODE_READ16
+#define JT_NODE_READ16 0  // node_step's LDS arm
+#endif
+template <bool OVF, bool NCACHE, bool WIDE, int F>
+__host__ __device__ constexpr bool node_baked() {
+    return JT_NODE_BAKE && !OVF && !NCACHE && !WIDE && ft_none(F);
+}
+__host__ __device__ constexpr int push_bit(bool baked) { return baked ? BAKE_MASK_BIT : 0; }
+
 __device__ __forceinline__ int neg_mask(v3 d, int flip) {
     return ((d.x < 0 ? 1 : 0) | (d.y < 0 ? 2 : 0) | (d.z < 0 ? 4 : 0)) ^ flip;
 }
 
-__device__ __forceinline__ void world_ray(const DScene& S, Trav& T) {
+__device__ __forceinline__ void world_ray(const DScene& S, Trav& T, int pb = 0) {
     T.lo = T.wo;
     T.ld = T.wd;
     T.ldinv = T.wdinv;
-    T.negmask = neg_mask(T.wd, query_flip(S, T));
+    T.negmask = neg_mask(T.wd, query_flip(S, T, pb));
     T.inst_space = 0;
 }
 
@@ -136,10 +159,11 @@ __device__ __forceinline__ void query_reset(Trav& T, int nh) {
     T.cur_kind = KIND_TRI;
     T.inst_space = 0;
 }
-__device__ __forceinline__ void query_begin(const DScene& S, Trav& T, v3 o, v3 d, unsigned root, int* stack, int rerun = 0) {
+__device__ __forceinline__ void query_begin(const DScene& S, Trav& T, v3 o, v3 d, unsigned root, int* stack, int rerun = 0,
+                                            int pb = 0) {
     query_ray(T, o, d);
     query_reset(T, rerun);
-    T.negmask = neg_mask(d, rerun ? 0 : S.order_flip);
+    T.negmask = neg_mask(d, (rerun ? 0 : S.order_flip) | pb);
     stack[0] = (int)root;
     T.sp = 1;
     T.low = 0;
@@ -160,9 +184,10 @@ __device__ __forceinline__ unsigned wroot_instance(int inst) { return W_LEAF | W
 // query_begin for either traversal: a closest-hit scene query, or (inst >= 0) the
 // intersect_instance_bvh of sample_lights_pdf
 template <bool WIDE>
-__device__ __forceinline__ void query_start(const DScene& S, Trav& T, v3 o, v3 d, int inst, int* stack, int rerun = 0) {
+__device__ __forceinline__ void query_start(const DScene& S, Trav& T, v3 o, v3 d, int inst, int* stack, int rerun = 0,
+                                            int pb = 0) {
     if (WIDE) query_begin_wide(S, T, o, d, inst < 0 ? WROOT_SCENE : wroot_instance(inst), rerun);
-    else query_begin(S, T, o, d, inst < 0 ? ((T_TLAS << 30) | SNAP_NONE) : ((T_INST << 30) | SNAP_NONE | (unsigned)inst), stack, rerun);
+    else query_begin(S, T, o, d, inst < 0 ? ((T_TLAS << 30) | SNAP_NONE) : ((T_INST << 30) | SNAP_NONE | (unsigned)inst), stack, rerun, pb);
 }
 // The scene query of a lane that has just run its bounce's light chains inline (light_chain with
 // JT_CHAIN_TAIL) in the binary traversal: query_begin for the same direction d, whose world-space
@@ -170,14 +195,14 @@ __device__ __forceinline__ void query_start(const DScene& S, Trav& T, v3 o, v3 d
 // left in T.negmask. The instance-space values of a transformed light (T.ldinv, T.negmask with
 // FT_XFORM) are never reused.
 template <int F>
-__device__ __forceinline__ void query_restart(const DScene& S, Trav& T, v3 o, v3 d, int* stack) {
+__device__ __forceinline__ void query_restart(const DScene& S, Trav& T, v3 o, v3 d, int* stack, int pb = 0) {
     T.wo = o;
     T.wd = d;
     T.lo = o;
     T.ld = d;
     T.ldinv = T.wdinv;
     query_reset(T, 0);
-    if (F & FT_XFORM) T.negmask = neg_mask(d, S.order_flip);
+    if (F & FT_XFORM) T.negmask = neg_mask(d, S.order_flip | pb);
     stack[0] = (int)((T_TLAS << 30) | SNAP_NONE);
     T.sp = 1;
     T.low = 0;
@@ -192,10 +217,10 @@ __device__ __forceinline__ void query_restart(const DScene& S, Trav& T, v3 o, v3
 // order in every child order, so it is never re-run (the oracle's instance_query: the same rule).
 constexpr int INST_LEAF_ROOT = 1 << 30;  // in the instance record's w (shape) word
 template <bool WIDE>
-__device__ __forceinline__ bool rerun_tie(const DScene& S, Trav& T, v3 o, v3 d, int inst, int* stack) {
+__device__ __forceinline__ bool rerun_tie(const DScene& S, Trav& T, v3 o, v3 d, int inst, int* stack, int pb = 0) {
     if (!JT_TIE_RERUN || (T.nh & (TIE_SEEN | REF_RERUN)) != TIE_SEEN || S.order_flip == 0) return false;
     if (inst >= 0 && (S.inst_blas[inst].w & INST_LEAF_ROOT)) return false;
-    query_start<WIDE>(S, T, o, d, inst, stack, REF_RERUN);
+    query_start<WIDE>(S, T, o, d, inst, stack, REF_RERUN, pb);
     return true;
 }
 
@@ -206,17 +231,17 @@ __device__ __forceinline__ bool rerun_tie(const DScene& S, Trav& T, v3 o, v3 d, 
 // XF false (kernels without FT_XFORM): every instance ray is the world ray, no transform, no
 // space switch.
 template <bool XF>
-__device__ __forceinline__ void enter_instance(const DScene& S, Trav& T, unsigned inst, const int4& ib) {
+__device__ __forceinline__ void enter_instance(const DScene& S, Trav& T, unsigned inst, const int4& ib, int pb = 0) {
     if (!XF || ib.y) {
         // inverse(identity) is exactly the identity: transform_ray returns the ray bit for bit
-        if (XF && T.inst_space) world_ray(S, T);
+        if (XF && T.inst_space) world_ray(S, T, pb);
     } else {
         const DInstTrav it = S.inst_trav[inst];
         const fr3 inv = frame_from(it.i0, it.i1, it.i2);
         T.lo = transform_point(inv, T.wo);
         T.ld = transform_vector(inv, T.wd);
         T.ldinv = V3(jl_rcp(T.ld.x), jl_rcp(T.ld.y), jl_rcp(T.ld.z));
-        T.negmask = neg_mask(T.ld, query_flip(S, T));
+        T.negmask = neg_mask(T.ld, query_flip(S, T, pb));
         T.inst_space = 1;
     }
     T.cur_inst = (int)inst;
@@ -326,16 +351,18 @@ template <int RING, bool OVF, int COUNT, bool NCACHE, int F>
 __device__ __forceinline__ void node_step(const DScene& S, Trav& T, int* stack, int pixel, Counters& cnt) {
     // without FT_XFORM every instance ray is the world ray: no transform, no space switch
     constexpr bool XF = (F & FT_XFORM) != 0;
+    constexpr bool BAKED = node_baked<OVF, NCACHE, false, F>();  // S.nodes holds the baked form (jt_push.h)
+    constexpr int PB = push_bit(BAKED);
     const unsigned e = st_pop<RING, OVF>(S, T, stack, pixel);
     unsigned type = e >> 30, idx = e & IDX_MASK;
     if (type == T_INST) {  // instance visit: inverse(frame, true) precomputed (src/bvh.jl:345,502)
         if (COUNT) cnt.instances++;
         const int4 ib = S.inst_blas[idx];  // blas_root, identity, kind, shape | leaf root (one load: x, y adjacent)
-        enter_instance<XF>(S, T, idx, ib);
+        enter_instance<XF>(S, T, idx, ib, PB);
         type = T_BLAS;
         idx = (unsigned)ib.x;
     } else if (XF && type == T_TLAS && T.inst_space) {
-        world_ray(S, T);  // back from an instance: TLAS nodes test the world ray
+        world_ray(S, T, PB);  // back from an instance: TLAS nodes test the world ray
     }
     const bool blas = type == T_BLAS;
     if (COUNT) cnt.nodes++;
@@ -356,7 +383,11 @@ __device__ __forceinline__ void node_step(const DScene& S, Trav& T, int* stack, 
         if (snap == 63u || snap != (unsigned)(T.nh & NH_COUNT))
             if (!intersect_bbox(T.lo, T.ldinv, ray_eps, T.tmax, S.nodes[idx].a, nb)) return;
     } else {  // LDS mode (no pre-test): the whole node, two LDS reads
-        const DNode nd = S.nodes[idx];
+        DNode nd = S.nodes[idx];
+        // JT_NODE_READ16 (baking kernels): the node as two 16-B reads issued together, as the
+        // NCACHE arm pins its nb, instead of 16 + 8 B and a dependent 8-B read of start/meta
+        // behind the box test. Not adopted: EXPERIMENTS.md.
+        if (JT_NODE_READ16 && BAKED) __asm__("" : "+v"(nd.b.x), "+v"(nd.b.y), "+v"(nd.b.z), "+v"(nd.b.w));
         if (!intersect_bbox(T.lo, T.ldinv, ray_eps, T.tmax, nd.a, nd.b)) return;
         nb = nd.b;
     }
@@ -368,6 +399,18 @@ __device__ __forceinline__ void node_step(const DScene& S, Trav& T, int* stack, 
         // (jt_push.h), so every lane writes PUSH_SLOTS entries straight-line — the surplus ones
         // repeat the top entry, or land in the slot just popped — instead of a divergent branch
         // per arm and a loop per TLAS-leaf instance. The leaf cursor is set by selects.
+        if constexpr (BAKED) {
+            // the node's words already hold what push_plan derives from them (start is e0); the
+            // writes are addressed from the slot just popped
+            const PushPlan p = push_plan_baked((unsigned)start, meta, T.negmask, T.sp);
+            int* const top = stack + T.sp * BLOCK;
+#pragma unroll
+            for (int j = 0; j < PUSH_SLOTS; j++) top[(p.slot[j] - T.sp) * BLOCK] = (int)p.value[j];
+            T.sp += p.npush;
+            T.prim = p.leaf ? start : T.prim;
+            T.nprim = p.leaf ? num : T.nprim;
+            return;
+        }
         const PushPlan p = push_plan(meta, start, type, blas, T.negmask, T.sp);
 #pragma unroll
         for (int j = 0; j < PUSH_SLOTS; j++) stack[p.slot[j] * BLOCK] = (int)p.value[j];
@@ -539,6 +582,7 @@ template <int COUNT, int F>
 __device__ __forceinline__ void inst_leaf_query(const DScene& S, Trav& T, v3 o, v3 d, v3 dinv, int negmask, int inst,
                                                 Counters& cnt) {
     constexpr bool XF = (F & FT_XFORM) != 0;
+    constexpr int PB = push_bit(node_baked<false, false, false, F>());  // chain_leaf_step's kernels: LDS mode, binary, fixed stack
     T.wo = o;
     T.wd = d;
     T.wdinv = dinv;
@@ -554,7 +598,7 @@ __device__ __forceinline__ void inst_leaf_query(const DScene& S, Trav& T, v3 o, 
     const int4 ib = S.inst_blas[inst];
     // the query has just started in world space (inst_space 0), so enter_instance's return to the
     // world ray is dead here; this overwrites query_reset's cur_inst and cur_kind
-    enter_instance<XF>(S, T, (unsigned)inst, ib);
+    enter_instance<XF>(S, T, (unsigned)inst, ib, PB);
     if (COUNT) cnt.nodes++;
     const DNode nd = S.nodes[ib.x];
     const bool pass = intersect_bbox(T.lo, T.ldinv, ray_eps, T.tmax, nd.a, nd.b);
