@@ -1,5 +1,7 @@
-// jt_denoise.h — the denoiser's checks and launch; the filter, its kernels, jt_denoise_image and
-// the context's half (jt_denoise, jt_get_denoised) are in jt_denoise.hip. Not part of the ABI.
+// jt_denoise.h — the two denoisers' checks and launches, thin fronts of the one parameter check
+// and the one launch loop in jt_denoise.hip; the kernels (demodulate_kernel<GUIDED>,
+// atrous_kernel<GUIDED, LAST>), the host-array entries and the context's half (jt_denoise,
+// jt_denoise_guided, jt_get_denoised) are there too. Not part of the ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -150,30 +150,28 @@ class TraceState:
         del n
         return alb, nrm, hits
 
+    def _denoised(self, entry: str, params, defaults, overrides) -> np.ndarray:
+        """The context filter `entry` (jt_denoise or jt_denoise_guided), then jt_get_denoised."""
+        if overrides and params is None:
+            params = defaults()
+        params = _with_overrides(params, overrides)
+        abi.check(self.lib, getattr(self.lib, entry)(self.handle, None if params is None else C.byref(params)))
+        out = np.empty((self.height, self.width, 4), np.float32)
+        abi.check(self.lib, self.lib.jt_get_denoised(self.handle, out.ctypes.data_as(abi.f32p)))
+        return out
+
     def denoise(self, params: abi.jt_denoise_params | None = None, **overrides) -> np.ndarray:
         """jt_denoise then jt_get_denoised: the (H, W, 4) float32 a-trous filter of the running
         means (include/jtrace.h). params None: the defaults for the samples traced so far;
         overrides replace single fields (iterations, sigma_color, ...) of either."""
-        if overrides and params is None:
-            params = denoise_defaults(self.samples, self.lib)
-        params = _with_overrides(params, overrides)
-        abi.check(self.lib, self.lib.jt_denoise(self.handle, None if params is None else C.byref(params)))
-        out = np.empty((self.height, self.width, 4), np.float32)
-        abi.check(self.lib, self.lib.jt_get_denoised(self.handle, out.ctypes.data_as(abi.f32p)))
-        return out
+        return self._denoised("jt_denoise", params, lambda: denoise_defaults(self.samples, self.lib), overrides)
 
     def denoise_guided(self, params: abi.jt_denoise_guided_params | None = None, **overrides) -> np.ndarray:
         """jt_denoise_guided then jt_get_denoised: the (H, W, 4) float32 variance-guided a-trous
         filter of the running means, its colour tolerance the per-pixel variance of
         jt_get_variance (include/jtrace.h). Needs k > 1 streams and two samples. params None: the
         defaults; overrides replace single fields (iterations, sigma_variance, ...) of either."""
-        if overrides and params is None:
-            params = denoise_guided_defaults(self.lib)
-        params = _with_overrides(params, overrides)
-        abi.check(self.lib, self.lib.jt_denoise_guided(self.handle, None if params is None else C.byref(params)))
-        out = np.empty((self.height, self.width, 4), np.float32)
-        abi.check(self.lib, self.lib.jt_get_denoised(self.handle, out.ctypes.data_as(abi.f32p)))
-        return out
+        return self._denoised("jt_denoise_guided", params, lambda: denoise_guided_defaults(self.lib), overrides)
 
     def variance(self) -> np.ndarray:
         """jt_get_variance: the (H, W, 4) float32 variance of the image per channel (of the mean,
@@ -265,23 +263,29 @@ def denoise_defaults(samples: int, lib=None) -> abi.jt_denoise_params:
     return p
 
 
+def _filter_host_arrays(lib, entry: str, arrays, channels, device, params, defaults, overrides) -> np.ndarray:
+    """The host-array filter `entry` (jt_denoise_image or jt_denoise_guided_image) on `arrays`,
+    the first the image and all in the entry's argument order, (H, W, n) for the n of `channels`."""
+    arrays = [np.ascontiguousarray(a, np.float32) for a in arrays]
+    rgba = arrays[0]
+    if rgba.ndim != 3 or any(a.shape != rgba.shape[:2] + (n,) for a, n in zip(arrays, channels)):
+        raise ValueError(f"expected {', '.join(f'(H, W, {n})' for n in channels)} arrays, "
+                         f"got {', '.join(str(a.shape) for a in arrays)}")
+    p = _with_overrides(params if params is not None else defaults(), overrides)
+    out = np.empty_like(rgba)
+    abi.check(lib, getattr(lib, entry)(*(a.ctypes.data_as(abi.f32p) for a in arrays), rgba.shape[1], rgba.shape[0],
+                                       C.byref(p), int(device), out.ctypes.data_as(abi.f32p)))
+    return out
+
+
 def denoise_image(rgba, albedo, normal, device: int = 0, params: abi.jt_denoise_params | None = None, samples: int = 1,
                   lib=None, **overrides) -> np.ndarray:
     """jt_denoise_image: the denoiser on host arrays (H, W, 4), (H, W, 3), (H, W, 3) -> (H, W, 4)
     float32, on HIP device `device`. params None: the defaults for `samples` samples per pixel;
     overrides replace single fields."""
     lib = lib or abi.load_library()
-    rgba = np.ascontiguousarray(rgba, np.float32)
-    albedo = np.ascontiguousarray(albedo, np.float32)
-    normal = np.ascontiguousarray(normal, np.float32)
-    if rgba.ndim != 3 or rgba.shape[2] != 4 or albedo.shape != rgba.shape[:2] + (3,) or normal.shape != albedo.shape:
-        raise ValueError(f"expected (H, W, 4), (H, W, 3), (H, W, 3) arrays, got {rgba.shape}, {albedo.shape}, {normal.shape}")
-    p = _with_overrides(params if params is not None else denoise_defaults(samples, lib), overrides)
-    out = np.empty_like(rgba)
-    abi.check(lib, lib.jt_denoise_image(rgba.ctypes.data_as(abi.f32p), albedo.ctypes.data_as(abi.f32p),
-                                        normal.ctypes.data_as(abi.f32p), rgba.shape[1], rgba.shape[0], C.byref(p),
-                                        int(device), out.ctypes.data_as(abi.f32p)))
-    return out
+    return _filter_host_arrays(lib, "jt_denoise_image", (rgba, albedo, normal), (4, 3, 3), device, params,
+                               lambda: denoise_defaults(samples, lib), overrides)
 
 
 def denoise_guided_defaults(lib=None) -> abi.jt_denoise_guided_params:
@@ -299,18 +303,5 @@ def denoise_guided_image(rgba, variance, albedo, normal, device: int = 0,
     (H, W, 3), (H, W, 3) -> (H, W, 4) float32, on HIP device `device`; variance as
     TraceState.variance() returns it. params None: the defaults; overrides replace single fields."""
     lib = lib or abi.load_library()
-    rgba = np.ascontiguousarray(rgba, np.float32)
-    variance = np.ascontiguousarray(variance, np.float32)
-    albedo = np.ascontiguousarray(albedo, np.float32)
-    normal = np.ascontiguousarray(normal, np.float32)
-    if (rgba.ndim != 3 or rgba.shape[2] != 4 or variance.shape != rgba.shape or albedo.shape != rgba.shape[:2] + (3,)
-            or normal.shape != albedo.shape):
-        raise ValueError(f"expected (H, W, 4), (H, W, 4), (H, W, 3), (H, W, 3) arrays, got {rgba.shape}, "
-                         f"{variance.shape}, {albedo.shape}, {normal.shape}")
-    p = _with_overrides(params if params is not None else denoise_guided_defaults(lib), overrides)
-    out = np.empty_like(rgba)
-    abi.check(lib, lib.jt_denoise_guided_image(rgba.ctypes.data_as(abi.f32p), variance.ctypes.data_as(abi.f32p),
-                                               albedo.ctypes.data_as(abi.f32p), normal.ctypes.data_as(abi.f32p),
-                                               rgba.shape[1], rgba.shape[0], C.byref(p), int(device),
-                                               out.ctypes.data_as(abi.f32p)))
-    return out
+    return _filter_host_arrays(lib, "jt_denoise_guided_image", (rgba, variance, albedo, normal), (4, 4, 3, 3), device,
+                               params, lambda: denoise_guided_defaults(lib), overrides)

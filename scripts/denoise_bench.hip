@@ -25,6 +25,32 @@
         }                                                                                 \
     } while (0)
 
+// the device time of one launch() on st, in ms
+template <class Launch>
+hipError_t timed(hipStream_t st, hipEvent_t e0, hipEvent_t e1, Launch launch, float* ms) {
+    hipError_t e;
+    if ((e = hipEventRecord(e0, st)) != hipSuccess || (e = launch()) != hipSuccess ||
+        (e = hipEventRecord(e1, st)) != hipSuccess || (e = hipEventSynchronize(e1)) != hipSuccess)
+        return e;
+    return hipEventElapsedTime(ms, e0, e1);
+}
+
+// one line per iteration count; returns the median of the I iterations
+double report(const char* filter, std::vector<std::vector<float>>& ms, int I, size_t np) {
+    const double compulsory = 64.0 * (double)np;  // d, albedo, normal read, d written: 64 B per pixel
+    double prev = 0;
+    for (int it = 1; it <= I; it++) {
+        std::sort(ms[it].begin(), ms[it].end());
+        const double med = ms[it][ms[it].size() / 2], mn = ms[it].front();
+        const double dt = med - prev;
+        std::printf("%siterations=%d  median %.4f ms  min %.4f ms  | step %2d (+demodulate at 1): %.4f ms, "
+                    "compulsory %.1f MB = %.2f TB/s\n",
+                    filter, it, med, mn, 1 << (it - 1), dt, compulsory / 1e6, compulsory / (dt * 1e-3) / 1e12);
+        prev = med;
+    }
+    return prev;
+}
+
 int main(int argc, char** argv) {
     const int W = argc > 1 ? std::atoi(argv[1]) : 1280, H = argc > 2 ? std::atoi(argv[2]) : 720;
     const int rounds = argc > 3 ? std::atoi(argv[3]) : 50;
@@ -63,50 +89,25 @@ int main(int argc, char** argv) {
     for (int r = -3; r < rounds; r++) {  // three warm-up rounds
         for (int it = 1; it <= I; it++) {
             jt_denoise_params q = p;
-            q.iterations = it;
-            CHECK(hipEventRecord(e0, st));
-            CHECK(jt::denoise_launch(st, d, d + np, d + 2 * np, W, H, q, d + 4 * np, d + 5 * np, d + 6 * np));
-            CHECK(hipEventRecord(e1, st));
-            CHECK(hipEventSynchronize(e1));
-            float t = 0;
-            CHECK(hipEventElapsedTime(&t, e0, e1));
-            if (r >= 0) ms[it].push_back(t);
             jt_denoise_guided_params gq = g;
-            gq.iterations = it;
-            CHECK(hipEventRecord(e0, st));
-            CHECK(jt::denoise_guided_launch(st, d, d + 3 * np, d + np, d + 2 * np, W, H, gq, d + 4 * np, d + 5 * np,
-                                            d + 6 * np));
-            CHECK(hipEventRecord(e1, st));
-            CHECK(hipEventSynchronize(e1));
-            CHECK(hipEventElapsedTime(&t, e0, e1));
+            q.iterations = gq.iterations = it;
+            float t = 0;
+            CHECK(timed(st, e0, e1, [&] {
+                return jt::denoise_launch(st, d, d + np, d + 2 * np, W, H, q, d + 4 * np, d + 5 * np, d + 6 * np);
+            }, &t));
+            if (r >= 0) ms[it].push_back(t);
+            CHECK(timed(st, e0, e1, [&] {
+                return jt::denoise_guided_launch(st, d, d + 3 * np, d + np, d + 2 * np, W, H, gq, d + 4 * np, d + 5 * np,
+                                                 d + 6 * np);
+            }, &t));
             if (r >= 0) gms[it].push_back(t);
         }
     }
     std::printf("denoise %dx%d, defaults for 16 spp, %d rounds, filters and iteration counts interleaved\n", W, H, rounds);
-    const double compulsory = 64.0 * (double)np;  // d, albedo, normal read, d written: 64 B per pixel
-    double prev = 0;
-    for (int it = 1; it <= I; it++) {
-        std::sort(ms[it].begin(), ms[it].end());
-        const double med = ms[it][ms[it].size() / 2], mn = ms[it].front();
-        const double dt = med - prev;
-        std::printf("iterations=%d  median %.4f ms  min %.4f ms  | step %2d (+demodulate at 1): %.4f ms, "
-                    "compulsory %.1f MB = %.2f TB/s\n",
-                    it, med, mn, 1 << (it - 1), dt, compulsory / 1e6, compulsory / (dt * 1e-3) / 1e12);
-        prev = med;
-    }
-    std::printf("one default denoise (%d iterations): median %.4f ms\n", I, prev);
-    const double plain = prev;
-    prev = 0;
-    for (int it = 1; it <= I; it++) {
-        std::sort(gms[it].begin(), gms[it].end());
-        const double med = gms[it][gms[it].size() / 2], mn = gms[it].front();
-        const double dt = med - prev;
-        std::printf("guided iterations=%d  median %.4f ms  min %.4f ms  | step %2d (+demodulate at 1): %.4f ms, "
-                    "compulsory %.1f MB = %.2f TB/s\n",
-                    it, med, mn, 1 << (it - 1), dt, compulsory / 1e6, compulsory / (dt * 1e-3) / 1e12);
-        prev = med;
-    }
-    std::printf("one default guided denoise (%d iterations): median %.4f ms, %.3f x the plain filter\n", I, prev,
-                prev / plain);
+    const double plain = report("", ms, I, np);
+    std::printf("one default denoise (%d iterations): median %.4f ms\n", I, plain);
+    const double guided = report("guided ", gms, I, np);
+    std::printf("one default guided denoise (%d iterations): median %.4f ms, %.3f x the plain filter\n", I, guided,
+                guided / plain);
     return 0;
 }
