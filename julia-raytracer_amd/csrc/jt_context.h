@@ -28,15 +28,11 @@ struct jt_ctx {
     int cus = 256;   // compute units of the device (persistent grid size)
     int lk = 0;      // log2 of the sample streams per pixel (DParams::lk; fixed at jt_create)
     int tiles = 0;   // 8x8 pixel tiles
-    int stack = 16;  // stack bound of the scene (entries); > 16: LDS ring of `ring` + HBM overflow
-    int ring = 16;
-    int feat = jtd::FT_ALL;   // scene feature bits (jt_records.h)
-    int kmask = jtd::FT_ALL;  // feature mask of the kernel specialisation the scene runs
-    bool wide = false;   // JT_TRAVERSAL_WIDE: the wide-record kernels (configurations 8-15)
-    int traversal = 0;   // jt_params.traversal as resolved (JT_TRAVERSAL_AUTO: near or wide)
+    // the kernel configuration the scene runs, its memory mode, stack and gates (select_kernel,
+    // jt_select.h), fixed at jt_create
+    jtk::KernelChoice choice{};
     bool env_alias = false;    // JT_ENV_ALIAS=1: environment lights sample through alias tables
                                // until jt_reset
-    size_t lds_scene_bytes = 0;  // > 0: small-scene LDS mode
     int count = 1;             // 1: all traversal counters (diagnostic), 0: paths/rays/light queries only
     bool exported = false;  // jt_get_device_buffers handed out the accumulators' device pointers
     bool failed = false;       // a launch failed: the running means are unusable

@@ -86,7 +86,7 @@ __device__ __forceinline__ float env_light_pdf(const DScene& S, const DLight l, 
 // in exactly the reference's order; only where the lane waits between them changes.
 // PH_FINISH: path done (in a light-hit step), sample not yet accumulated
 enum : int { PH_SCENE = 0, PH_LIGHT = 1, PH_FINISH = 2 };
-// light_steps(sampler, F), the kernels with light-hit steps: jt_launch.h
+// light_steps(sampler, F), the kernels with light-hit steps: jt_select.h
 // the scene's light chains run inline: known at compile time (FT_LINL) or checked at run time
 __device__ __forceinline__ bool chains_inline(int F, const DScene& S) { return !(F & FT_NOIL) && ((F & FT_LINL) || S.light_inline); }
 enum : int { F_HIT = 1, F_VOLUME = 2 };
@@ -281,7 +281,7 @@ __device__ __forceinline__ bool light_hit(const DScene& S, const DParams& P, Pat
 // before (A/B runs).
 // Adopted per kernel family where measured not slower (EXPERIMENTS.md): not in the wide kernels
 // (not measured), not in FT_MESH's (bathroom1: -0.6 %, its chains keep the re-run loop); the light-steps kernel
-// (FT_NONE without FT_LINL) never runs a chain inline (kernel_mask) and keeps its compiled form.
+// (FT_NONE without FT_LINL) never runs a chain inline (select_kernel) and keeps its compiled form.
 #ifndef JT_CHAIN_TAIL
 #define JT_CHAIN_TAIL 2
 #endif

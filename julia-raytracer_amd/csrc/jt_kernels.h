@@ -1,6 +1,7 @@
 // jt_kernels.h — the MI355X (gfx950) path-tracing megakernel: the kernel body, the two kernels and
 // their launch. Its per-lane device functions are in jt_scene_eval.h, jt_traverse.h and
-// jt_integrator.h; what the host needs of it (argument records, masks, configurations) in jt_launch.h.
+// jt_integrator.h; what the host needs of it in jt_launch.h (argument records) and jt_select.h
+// (masks, configurations).
 //
 // Replaces trace_samples (Princic-1837592/julia-raytracer src/trace.jl:215-274) and everything
 // it calls per (pixel, sample, bounce): trace_sample :584, trace_path :276 / trace_naive :471,
@@ -16,7 +17,7 @@
 // mean (lerp with w = 1/(s+1), src/trace.jl:631-648) is kept in LDS across samples and
 // written once per work unit.
 //
-// Build: every kernel configuration (JT_LAUNCH_CONFIG, jt_launch.h) is instantiated in its own
+// Build: every kernel configuration (CONFIGS, jt_select.h) is instantiated in its own
 // translation unit (jt_kv.hip, compiled once per configuration, the only file that includes this
 // header) so the kernels compile in parallel; the host context (jt_trace.hip) only declares them
 // (jt_launch.h). The records the kernels read are declared in jt_records.h (through jt_device.h)

@@ -1,4 +1,4 @@
-// jt_kv.hip — one kernel configuration of the megakernel (jt_kernels.h; LaunchConfig<JT_VARIANT>, jt_launch.h),
+// jt_kv.hip — one kernel configuration of the megakernel (jt_kernels.h; LaunchConfig<JT_VARIANT>, jt_select.h),
 // instantiated for both samplers and both counter levels. The Makefile compiles this file once
 // per configuration (-DJT_VARIANT=0..NUM_LAUNCH_CONFIGS-1), so the kernels build in parallel.
 #include "jt_kernels.h"
@@ -9,5 +9,5 @@
 
 namespace jtk {
 static_assert(JT_VARIANT >= 0 && JT_VARIANT < NUM_LAUNCH_CONFIGS, "JT_VARIANT out of range");
-JT_KV_FOR(JT_VARIANT, template)
+JT_KV_INSTANTIATE(JT_VARIANT)
 }  // namespace jtk

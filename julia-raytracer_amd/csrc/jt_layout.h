@@ -32,8 +32,8 @@ inline const char* opt(const Options& opts, const char* k) {  // an option's val
 }
 
 // traversal stack entries and wide child words carry a 24-bit node / record / instance index
-// (jtk::IDX_MASK, jt_launch.h; jt_trace.hip asserts they agree)
-constexpr unsigned IDX_MASK = (1u << 24) - 1;
+// (jt_select.h)
+using jtk::IDX_MASK;
 
 struct HostScene {
 #define JT_ARRAY_VECTOR(T, name) std::vector<T> name;

@@ -26,7 +26,7 @@
 namespace jtk {
 
 constexpr int PUSH_SLOTS = 4;  // the most entries one node step pushes (a full TLAS leaf)
-// stack entry fields (jt_launch.h): type in bits 30-31, the child pre-test snapshot in 24-29
+// stack entry fields (jt_select.h): type in bits 30-31, the child pre-test snapshot in 24-29
 constexpr unsigned PUSH_T_INST = 1u, PUSH_SNAP_NONE = 63u << 24;
 
 struct PushPlan {

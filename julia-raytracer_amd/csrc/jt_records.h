@@ -7,10 +7,8 @@
 #include <stdint.h>
 
 #include "jt_plan.h"  // the stream-count constants (JT_MAX_STREAMS, JT_STREAM_ITEMS_MAX, ...)
+#include "jt_select.h"  // the feature bits (FT_*), the launch constants and the kernel choice
 
-#ifndef JT_AUTO_WIDE_MIN_STACK
-#define JT_AUTO_WIDE_MIN_STACK 32  // JT_TRAVERSAL_AUTO: wide records for HBM-mode scenes deeper than this
-#endif
 // jt_trace_range defers its range until this many samples are queued (jt_ctx::pend0)
 #define JT_DEFER_SAMPLES 64
 #ifndef JT_EXACT_MATH
@@ -62,30 +60,6 @@ struct alignas(16) DInstShade {
     int rot_identity;  // frame x, y, z are exactly the unit axes: element normals from enrm_id
 };
 enum { KIND_TRI = 0, KIND_QUAD = 1 };
-// Scene feature bits of a kernel specialisation (chosen per scene by jt_create): a kernel built
-// without a bit assumes the scene has none of it, so the branches it guards are compiled out.
-// FT_ALL is the general kernel; FT_NONE serves scenes of matte triangles without textures,
-// vertex attributes, environments or opacity (cornellbox); jt_create picks the smallest compiled
-// mask that covers the scene (jt_trace.hip, launch_s). Results are bit-identical.
-enum : int {
-    FT_TEX = 1,    // material textures (incl. normal maps)
-    FT_ATTR = 2,   // shape normals / texcoords / colors
-    FT_QUAD = 4,   // quad shapes
-    FT_MAT = 8,    // materials other than matte
-    FT_ENV = 16,   // environments (escaped rays, environment lights)
-    FT_OPAC = 32,  // opacity < 1 possible (material opacity, color-texture or vertex-color alpha)
-    FT_VOL = 64,   // refractive / subsurface / volumetric materials (the volume stack)
-    FT_XFORM = 128,  // instances whose inverse frame is not exactly the identity
-    FT_NONE = 0,
-    FT_ALL = 255,
-    // kernel build flag, not a scene feature: the scene's light chains run inline
-    // (DScene::light_inline; jt_integrator.h light_chain), so the kernel has no light-hit steps
-    FT_LINL = 8192,
-    // kernel build flag: the scene has no instance light (sample_lights_pdf never queries a BVH)
-    FT_NOIL = 16384
-};
-// a kernel mask of no scene feature (the FT_NONE kernels, with or without the FT_LINL build flag)
-__host__ __device__ constexpr bool ft_none(int F) { return (F & ~(FT_LINL | FT_NOIL)) == FT_NONE; }
 struct alignas(16) DShape {
     int kind, blas_root, prim_base, idx_base;
     int pos_base, nrm_base, tc_base, col_base;  // -1 = absent

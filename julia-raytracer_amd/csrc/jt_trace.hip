@@ -1,8 +1,8 @@
 // jt_trace.hip — the C-ABI device context of the MI355X path tracer (include/jtrace.h, jt_ctx in
 // jt_context.h): the kernel dispatch, scene upload (the steps of jt_create), the sample queue
 // and its launches, the single-device getters. The scene's validation and host layout are in
-// jt_layout.cpp (no HIP runtime), the launch plan's integer rules in jt_plan.h, the trace kernels
-// in jt_kernels.h (instantiated by jt_kv.hip, one translation unit per configuration; this unit
+// jt_layout.cpp (no HIP runtime), the launch plan's integer rules in jt_plan.h, the choice of the
+// scene's kernel configuration in jt_select.h (select_kernel), the trace kernels in jt_kernels.h (instantiated by jt_kv.hip, one translation unit per configuration; this unit
 // sees only their declarations and the argument records, jt_launch.h), the
 // combine and chain kernels in jt_accum.hip, the multi-device context in jt_multi.hip, and the
 // denoiser's and the error estimate's entry points beside their kernels (jt_denoise.hip,
@@ -10,11 +10,14 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
+#include <cassert>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "jt_accum.h"
@@ -25,51 +28,19 @@ using namespace jtd;
 using namespace jtk;
 using namespace jtc;
 
-namespace jtk {
-// every configuration is compiled in its own translation unit (jt_kv.hip)
-JT_KV_FOR(0, extern template)
-JT_KV_FOR(1, extern template)
-JT_KV_FOR(2, extern template)
-JT_KV_FOR(3, extern template)
-JT_KV_FOR(4, extern template)
-JT_KV_FOR(5, extern template)
-JT_KV_FOR(6, extern template)
-JT_KV_FOR(7, extern template)
-JT_KV_FOR(8, extern template)
-JT_KV_FOR(9, extern template)
-JT_KV_FOR(10, extern template)
-JT_KV_FOR(11, extern template)
-JT_KV_FOR(12, extern template)
-JT_KV_FOR(13, extern template)
-JT_KV_FOR(14, extern template)
-JT_KV_FOR(15, extern template)
-
-// configuration ID of the binary traversal, or its wide twin (ID + NUM_BASE_CONFIGS)
-template <int ID, int SAMPLER, int COUNT>
-hipError_t launch_tw(bool wide, const DScene& S, const DParams& P, int s0, int s1, const DAccum& A, hipStream_t st, int cus) {
-    return wide ? launch_cfg<ID + NUM_BASE_CONFIGS, SAMPLER, COUNT>(S, P, s0, s1, A, st, cus)
-                : launch_cfg<ID, SAMPLER, COUNT>(S, P, s0, s1, A, st, cus);
+namespace {
+// The launch functions of every configuration (jt_kv.hip compiles each in its own translation
+// unit), indexed [KernelChoice::id][sampler - 1][counter level]
+using LaunchFn = hipError_t (*)(const DScene&, const DParams&, int, int, const DAccum&, hipStream_t, int);
+struct LaunchRow {
+    LaunchFn fn[2][2];
+};
+template <int... ID>
+constexpr std::array<LaunchRow, sizeof...(ID)> launch_table(std::integer_sequence<int, ID...>) {
+    return {{LaunchRow{{{launch_cfg<ID, 1, 0>, launch_cfg<ID, 1, 1>}, {launch_cfg<ID, 2, 0>, launch_cfg<ID, 2, 1>}}}...}};
 }
-// Stack configurations: the whole bound in a 16-entry LDS ring, or a RING-entry ring + HBM.
-template <int SAMPLER, int COUNT>
-hipError_t launch_s(int need, int ring, int kmask, bool wide, const DScene& S, const DParams& P, int s0, int s1,
-                    const DAccum& A, hipStream_t st, int cus) {
-    if (need <= 16) {
-        if (kmask == (FT_NONE | FT_LINL)) return launch_tw<0, SAMPLER, COUNT>(wide, S, P, s0, s1, A, st, cus);
-        if (kmask == FT_NONE) return launch_tw<7, SAMPLER, COUNT>(wide, S, P, s0, s1, A, st, cus);
-        return launch_tw<1, SAMPLER, COUNT>(wide, S, P, s0, s1, A, st, cus);
-    }
-    if (ring <= 16) {
-        switch (kmask) {
-            case FT_MESH | FT_LINL: return launch_tw<2, SAMPLER, COUNT>(wide, S, P, s0, s1, A, st, cus);
-            case FT_MESH_ENV | FT_NOIL: return launch_tw<3, SAMPLER, COUNT>(wide, S, P, s0, s1, A, st, cus);
-            case FT_MESH_ENV_QUAD | FT_LINL: return launch_tw<4, SAMPLER, COUNT>(wide, S, P, s0, s1, A, st, cus);
-            default: return launch_tw<5, SAMPLER, COUNT>(wide, S, P, s0, s1, A, st, cus);
-        }
-    }
-    return launch_tw<6, SAMPLER, COUNT>(wide, S, P, s0, s1, A, st, cus);
-}
-}  // namespace jtk
+constexpr auto LAUNCH = launch_table(std::make_integer_sequence<int, NUM_LAUNCH_CONFIGS>{});
+}  // namespace
 
 int jtc::hip_fail(hipError_t e, const char* what) {
     return jt::fail(JT_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
@@ -102,54 +73,41 @@ int upload(jt_ctx* c, const std::vector<T>& host, const T** dptr) {
 constexpr size_t SCHED_BYTES = (size_t)NBANDS * BAND_STRIDE * 4;
 
 // ------------------------------------------------------------------------ the steps of jt_create
-static_assert(jt::IDX_MASK == jtk::IDX_MASK, "the layout's index limit is the kernels'");
-
-// A scene ready for upload: its host layout (jt_layout.h) and what depends on the kernels' LDS use
+// A scene ready for upload: its host layout (jt_layout.h) and the kernel it runs (jt_select.h)
 struct PreparedScene {
     jt::HostScene hs;
-    int ring = 16;               // entries of the overflow kernels' LDS stack ring (option lds_stack)
-    size_t lds_scene_bytes = 0;  // > 0: small-scene LDS mode, the bytes of the blob
-    int traversal = 0;           // jt_params.traversal, JT_TRAVERSAL_AUTO resolved to near or wide
+    KernelChoice choice;
 };
 
-// The bytes of the LDS blob when the scene runs from it, 0 for HBM mode.
-// LDS mode only when the blob does not cost workgroups per CU: the kernel holds at most
-// 4 workgroups per CU (4 waves/SIMD), so the blob + stack + accumulators may use up to
-// 160 KiB / 4, or as much as HBM mode's stack + accumulators already cost. Override
-// with the option lds_scene=0 (off) or a byte budget for the blob.
-size_t lds_mode_bytes(const jt::HostScene& hs, int ring, const jt::Options& opts) {
-    size_t budget = 48 * 1024;
-    if (const char* v = jt::opt(opts, "lds_scene")) budget = (size_t)std::atoll(v);
-    // HBM mode's stack is the kernel's static ring (16 or 32 entries); LDS mode's, without
-    // overflow, just the scene's bound
-    // + the texel-decode LUTs a texture kernel keeps in LDS (trace_body)
-    const size_t acc_bytes = (size_t)ACC_SLOTS * BLOCK * 4 + ((hs.feat & FT_TEX) ? 2048 : 0);
-    const size_t base_bytes = (size_t)(hs.need <= 16 ? 16 : ring) * BLOCK * 4 + acc_bytes;
-    const size_t lds_base = lds_stack_bytes(hs.need > 16, ring, hs.need) + acc_bytes;
-    const size_t bytes = hs.blob.size() * 16;
-    const size_t lds_cu = 160 * 1024;
-    const size_t wg_hbm = std::min<size_t>(4, lds_cu / base_bytes), wg_lds = lds_cu / (lds_base + bytes);
-    return bytes <= budget && wg_lds >= wg_hbm ? bytes : 0;
+// the options that bear on the kernel choice, as select_kernel's integer inputs
+void select_options(const jt::Options& opts, SelectIn& in) {
+    if (const char* v = jt::opt(opts, "lds_scene")) in.lds_scene = (size_t)std::atoll(v);
+    if (const char* r = jt::opt(opts, "lds_stack")) in.lds_stack = std::atoi(r) > 16 ? 32 : 16;
+    if (const char* r = jt::opt(opts, "test_lds_ring")) in.test_lds_ring = std::atoi(r);
+    if (const char* wl = jt::opt(opts, "wait_lanes")) in.wait_lanes = given_lanes(std::atoi(wl), 64);
+    if (const char* ll = jt::opt(opts, "light_lanes")) in.light_lanes = given_lanes(std::atoi(ll), 65);
 }
 
-// Host only: the layout, the LDS / HBM decision and the traversal JT_TRAVERSAL_AUTO resolves to.
+// Host only: the layout and the kernel choice, with the wide records when it is a wide kernel.
 int prepare_scene(const jt_scene* scene, const jt_scene_bvh* bvh, const jt_lights* lights, const jt_params* params,
                   const jt::Options& opts, PreparedScene& ps) {
     jt::HostScene& hs = ps.hs;
     int st = jt::layout_scene(scene, bvh, lights, params, opts, hs);
     if (st != JT_OK) return st;
-    if (const char* r = jt::opt(opts, "lds_stack")) ps.ring = std::atoi(r) > 16 ? 32 : 16;
-    ps.lds_scene_bytes = lds_mode_bytes(hs, ps.ring, opts);
-    // auto: wide for a scene in HBM mode whose BVH is deep (a stack bound above 32: bathroom1 46,
-    // ecosys 43: +20 %, +30 % over near); near otherwise — features2 (bound 24) runs 2737/2742
-    // Mrays/s near vs 2677/2646 wide at 512 spp (gpurun_out/r04m), cornellbox runs from LDS
-    if (params->traversal == JT_TRAVERSAL_AUTO && !ps.lds_scene_bytes && hs.need > JT_AUTO_WIDE_MIN_STACK) {
-        // HBM mode: the wide records (the binary nodes stay uploaded, unused); the instances'
-        // BLAS roots become root records
-        if ((st = jt::make_wide(hs, scene, bvh)) != JT_OK) return st;
-    }
-    ps.traversal = params->traversal == JT_TRAVERSAL_AUTO ? (hs.wide ? JT_TRAVERSAL_WIDE : JT_TRAVERSAL_NEAR)
-                                                          : params->traversal;
+    SelectIn in;
+    in.feat = hs.feat;
+    in.need = hs.need;
+    in.blob_bytes = hs.blob.size() * 16;
+    in.inst_light = hs.inst_light;
+    in.light_inline = hs.S.light_inline != 0;
+    in.traversal = params->traversal;
+    in.sampler = params->sampler;
+    select_options(opts, in);
+    ps.choice = select_kernel(in);
+    // JT_TRAVERSAL_AUTO resolved to wide (HBM mode): the wide records (the binary nodes stay
+    // uploaded, unused); the instances' BLAS roots become root records
+    if (ps.choice.wide && !hs.wide && (st = jt::make_wide(hs, scene, bvh)) != JT_OK) return st;
+    assert(ps.choice.wide == hs.wide);
     return JT_OK;
 }
 
@@ -165,7 +123,7 @@ int upload_scene(jt_ctx* c, const PreparedScene& ps) {
 #undef JT_UPLOAD
     S.blob = nullptr;
     S.blob_n16 = 0;
-    if (ps.lds_scene_bytes) {
+    if (ps.choice.lds_scene_bytes) {
         if ((st = upload(c, hs.blob, &S.blob)) != JT_OK) return st;
         S.blob_n16 = (int)hs.blob.size();
     }
@@ -173,23 +131,14 @@ int upload_scene(jt_ctx* c, const PreparedScene& ps) {
 }
 
 // the stack members of the device scene and, for a bound above the LDS ring, its HBM overflow
-int alloc_stack_overflow(jt_ctx* c, const jt::Options& opts) {
+int alloc_stack_overflow(jt_ctx* c) {
     DScene& S = c->S;
-    const int need = c->stack;
+    const int need = c->choice.stack_need;
     S.ovf = nullptr;
     S.ovf_stride = 0;
-    S.ring = c->ring;
-    S.stack_need = c->stack;
-    // option test_lds_ring (tests only): use fewer ring entries than allocated, to exercise the overflow
-    if (const char* r = jt::opt(opts, "test_lds_ring")) {
-        int v = std::atoi(r);
-        if (v >= 1 && v <= 16 && (v & (v - 1)) == 0) {
-            S.ring = v;
-            c->stack = std::max(c->stack, 17);  // force the overflow-capable kernel
-            c->ring = 16;
-        }
-    }
-    if (c->stack > 16) {  // HBM overflow of the LDS stack ring: `need` entries per lane of the
+    S.ring = c->choice.ring_used;
+    S.stack_need = need;
+    if (c->choice.ovf) {  // HBM overflow of the LDS stack ring: `need` entries per lane of the
         // persistent grid (at most 8 workgroups of BLOCK lanes per CU resident; kernel slot
         // blockIdx.x * BLOCK + threadIdx.x: a query never outlives its lane)
         void* p = nullptr;
@@ -201,10 +150,9 @@ int alloc_stack_overflow(jt_ctx* c, const jt::Options& opts) {
     return JT_OK;
 }
 
-// DParams: camera, tile share, sample streams, wait lanes and light lanes; the kernel mask.
+// DParams: camera, tile share, sample streams, the kernel choice's wait lanes and light lanes.
 // forced_streams: the option "streams" set the stream count
-int make_params(jt_ctx* c, const jt_scene* scene, const jt_params* params, const jt::Options& opts, bool inst_light,
-                bool& forced_streams) {
+int make_params(jt_ctx* c, const jt_scene* scene, const jt_params* params, const jt::Options& opts, bool& forced_streams) {
     DParams& P = c->P;
     const int W = c->width, H = c->height;
     const jt_camera& cam = scene->cameras[params->camera];
@@ -253,23 +201,8 @@ int make_params(jt_ctx* c, const jt_scene* scene, const jt_params* params, const
         while ((1 << c->lk) < k) c->lk++;
     }
     P.lk = c->lk;
-    // measured best (cornellbox): 40 waiting lanes per shading phase; 48 with
-    // light-hit steps in the traversal phase (they take the light queries out of the phases)
-    c->kmask = kernel_mask(c->feat, c->stack, c->ring, c->lds_scene_bytes > 0, c->S.light_inline != 0, inst_light);
-    // light queries leave the shading phase's waiting lanes early (light-hit steps) or never wait
-    // there at all (inline chains): the gate then waits for more lanes
-    const int smp = c->sampler == JT_SAMPLER_NAIVE ? 2 : 1;
-    const bool lstep = inst_light && smp == 1 && (light_steps(smp, c->kmask) || c->S.light_inline);
-    // deep BVHs (stack bound > 32: bathroom1, ecosys) shade sooner: their lanes finish queries far
-    // apart, so waiting for many leaves the wave idle. Re-swept in round 4 (per-lane work items,
-    // short chunks, auto traversal; profiles/r04_ab/wait_lanes_r04o.txt): cornellbox 56 (52
-    // even, 48 / 60 -1.3 %, 64 -6 %), features2 56 (60 -2.9 %, 48 -0.5 %, 64 -9 %), bathroom1 40
-    // (48 even, 24 -10 %), ecosys (no instance lights) 24 (16 -1.2 %, 32 -2.2 %, 8 -11 %)
-    const bool deep = c->stack > 32;
-    P.wait_lanes = lstep ? (deep ? 40 : 56) : deep ? 24 : 40;
-    if (const char* wl = jt::opt(opts, "wait_lanes")) P.wait_lanes = std::max(1, std::min(64, std::atoi(wl)));
-    P.light_lanes = 2;
-    if (const char* ll = jt::opt(opts, "light_lanes")) P.light_lanes = std::max(1, std::min(65, std::atoi(ll)));
+    P.wait_lanes = c->choice.wait_lanes;
+    P.light_lanes = c->choice.light_lanes;
     return JT_OK;
 }
 
@@ -371,13 +304,8 @@ int jt_create(const jt_scene* scene, const jt_scene_bvh* bvh, const jt_lights* l
     c->total_samples = params->samples;
     c->batch = params->batch;
     c->sampler = params->sampler;
-    c->stack = ps.hs.need;
-    c->ring = ps.ring;
-    c->feat = ps.hs.feat;
-    c->wide = ps.hs.wide;
-    c->traversal = ps.traversal;
+    c->choice = ps.choice;
     c->env_alias = ps.hs.env_alias;
-    c->lds_scene_bytes = ps.lds_scene_bytes;
     auto bail = [&](int status) {
         jt_destroy(c);
         return status;
@@ -389,8 +317,8 @@ int jt_create(const jt_scene* scene, const jt_scene_bvh* bvh, const jt_lights* l
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, params->device) == hipSuccess && cus > 0) c->cus = cus;
 
     bool forced_streams = false;
-    if ((st = upload_scene(c, ps)) || (st = alloc_stack_overflow(c, opts)) ||
-        (st = make_params(c, scene, params, opts, ps.hs.inst_light, forced_streams)) ||
+    if ((st = upload_scene(c, ps)) || (st = alloc_stack_overflow(c)) ||
+        (st = make_params(c, scene, params, opts, forced_streams)) ||
         (st = alloc_accumulators(c, forced_streams)) || (st = jt_reset(c)))
         return bail(st);
     *out = c;
@@ -417,14 +345,14 @@ int jt_debug_layout_digest(const jt_scene* scene, const jt_scene_bvh* bvh, const
 #define JT_DIGEST(T, name) item(#name, hs.name.size(), hs.name.data(), hs.name.size() * sizeof(T));
     JT_SCENE_ARRAYS(JT_DIGEST, JT_DIGEST)
 #undef JT_DIGEST
-    const size_t blob_n16 = ps.lds_scene_bytes ? hs.blob.size() : 0;
+    const size_t blob_n16 = ps.choice.lds_scene_bytes ? hs.blob.size() : 0;
     item("blob", blob_n16, hs.blob.data(), blob_n16 * 16);
     std::snprintf(line, sizeof line,
                   "scalars need=%d feat=%d traversal=%d tlas_nnodes=%d tlas_wnodes=%d order_flip=%d light_inline=%d "
                   "o_nodes=%d o_wnodes=%d o_prims=%d o_inst_trav=%d o_inst_blas=%d o_inst_shade=%d o_shapes=%d o_pos=%d o_nrm=%d "
                   "o_tc=%d o_col=%d o_elems=%d o_enrm=%d o_enrm_id=%d o_materials=%d o_lights=%d o_cdf=%d o_light_hit=%d "
                   "o_light_elems=%d blob_n16=%d\n",
-                  hs.need, hs.feat, ps.traversal, S.tlas_nnodes, S.tlas_wnodes, S.order_flip, S.light_inline, S.o_nodes, S.o_wnodes,
+                  hs.need, hs.feat, ps.choice.traversal, S.tlas_nnodes, S.tlas_wnodes, S.order_flip, S.light_inline, S.o_nodes, S.o_wnodes,
                   S.o_prims, S.o_inst_trav, S.o_inst_blas, S.o_inst_shade, S.o_shapes, S.o_pos, S.o_nrm, S.o_tc, S.o_col, S.o_elems,
                   S.o_enrm, S.o_enrm_id, S.o_materials, S.o_lights, S.o_cdf, S.o_light_hit, S.o_light_elems, (int)blob_n16);
     text += line;
@@ -558,12 +486,7 @@ int ensure_chunk(jt_ctx* c) {
 int launch_range(jt_ctx* c, const DParams& P, const DAccum& A, int32_t s0, int32_t s1) {
     hipError_t e = hipMemsetAsync(c->A.work, 0, SCHED_BYTES, c->stream);
     if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync schedule");
-    if (c->sampler == JT_SAMPLER_NAIVE)
-        e = c->count ? launch_s<2, 1>(c->stack, c->ring, c->kmask, c->wide, c->S, P, s0, s1, A, c->stream, c->cus)
-                     : launch_s<2, 0>(c->stack, c->ring, c->kmask, c->wide, c->S, P, s0, s1, A, c->stream, c->cus);
-    else
-        e = c->count ? launch_s<1, 1>(c->stack, c->ring, c->kmask, c->wide, c->S, P, s0, s1, A, c->stream, c->cus)
-                     : launch_s<1, 0>(c->stack, c->ring, c->kmask, c->wide, c->S, P, s0, s1, A, c->stream, c->cus);
+    e = LAUNCH[c->choice.id].fn[c->sampler == JT_SAMPLER_NAIVE ? 1 : 0][c->count ? 1 : 0](c->S, P, s0, s1, A, c->stream, c->cus);
     if (e != hipSuccess) return hip_fail(e, "trace kernel launch");
     return JT_OK;
 }
@@ -788,23 +711,22 @@ extern "C" int jt_debug_stamps(jt_ctx* c, unsigned long long* out8) {
 int jt_describe(const jt_ctx* c, char* buf, int32_t n) {
     if (!c || !buf || n <= 0) return jt::fail(JT_ERR_INVALID, "NULL argument");
     if (c->multi) return multi_describe(c, buf, n);
-    const bool ovf = c->stack > 16;
-    const int ring = ovf ? c->ring : 16;
+    const KernelChoice& k = c->choice;
     // test-only options in effect (jt_set_option): a tile filter, a shortened LDS ring
     char filt[96] = "";
-    if (c->P.tile_stride != 1 || c->S.ring != c->ring)
+    if (c->P.tile_stride != 1 || k.ring_shortened())
         std::snprintf(filt, sizeof filt, " tile_filter=%d/%d ring_used=%d", c->P.tile_offset, c->P.tile_stride, c->S.ring);
     char tmp[640];
     std::snprintf(tmp, sizeof tmp,
                   "kernel=%s<%d,%d,%s,%d,%d,%s> mode=%s scene_lds_bytes=%zu stack_bound=%d lds_ring=%d hbm_overflow=%d "
                   "wait_lanes=%d light_lanes=%d streams=%d tiles=%d block=%d env_alias=%d light_inline=%d "
                   "traversal=%s%s",
-                  c->lds_scene_bytes ? "trace_kernel_lds" : "trace_kernel", c->sampler == JT_SAMPLER_NAIVE ? 2 : 1,
-                  ring, ovf ? "true" : "false", c->count, c->kmask, c->wide ? "true" : "false",
-                  c->lds_scene_bytes ? "lds" : "hbm", c->lds_scene_bytes,
-                  c->stack, ring, ovf ? 1 : 0, c->P.wait_lanes, c->P.light_lanes, 1 << c->lk, c->tiles, BLOCK,
+                  k.lds_scene_bytes ? "trace_kernel_lds" : "trace_kernel", c->sampler == JT_SAMPLER_NAIVE ? 2 : 1,
+                  k.ring, k.ovf ? "true" : "false", c->count, k.kmask, k.wide ? "true" : "false",
+                  k.lds_scene_bytes ? "lds" : "hbm", k.lds_scene_bytes,
+                  k.stack, k.ring, k.ovf ? 1 : 0, c->P.wait_lanes, c->P.light_lanes, 1 << c->lk, c->tiles, BLOCK,
                   c->env_alias ? 1 : 0, c->S.light_inline,
-                  c->traversal == JT_TRAVERSAL_REFERENCE ? "reference" : c->traversal == JT_TRAVERSAL_NEAR ? "near" : "wide",
+                  k.traversal == JT_TRAVERSAL_REFERENCE ? "reference" : k.traversal == JT_TRAVERSAL_NEAR ? "near" : "wide",
                   filt);
     std::snprintf(buf, (size_t)n, "%s", tmp);
     return JT_OK;

@@ -18,7 +18,7 @@ namespace jtk {
 using namespace jtd;
 
 // ============================================================================ traversal (src/bvh.jl)
-// The unified per-lane stack in LDS, its entry format and BLOCK, T_*, IDX_MASK, SNAP_NONE: jt_launch.h.
+// The unified per-lane stack in LDS, its entry format and BLOCK, T_*, IDX_MASK, SNAP_NONE: jt_select.h.
 
 struct Hit {
     int inst, elem;
