@@ -21,6 +21,8 @@
  *   jt_get_variance    (the build's own) the per-pixel variance of the image, from the spread of
  *                      the sample streams' means; jt_get_noise its image-level relative RMS error
  *   jt_denoise_guided  (the build's own) the a-trous filter with that variance as its colour tolerance
+ *   jt_adapt           (the build's own) adaptive sampling: 8x8 tiles whose variance meets a noise
+ *                      target take no more samples; jt_get_sample_counts the samples per pixel
  *   jt_destroy / jt_last_error — lifetime and error reporting (the reference throws Julia exceptions)
  *
  * Host helpers (run on the CPU, no device needed) that restate the reference's host code
@@ -501,6 +503,44 @@ int jt_denoise_guided_image(const float* rgba, const float* variance, const floa
  * a one-stream context (batch 1 without the option streams) or n < 2. */
 int jt_get_variance(jt_ctx* ctx, float* var_rgba);   /* W*H*4, variance of the mean per channel */
 int jt_get_noise(jt_ctx* ctx, double* noise);
+
+/* ---- adaptive sampling ------------------------------------------------------------------ */
+/* jt_adapt freezes the 8x8 tiles whose error estimate already meets the image-level noise target
+ * T; from then on every jt_trace_range / jt_trace_samples of the context skips them, so the
+ * samples go where the noise is. It decides only where samples go: when to stop stays the
+ * caller's (jt_get_noise <= T; waiting for every tile to freeze takes far longer).
+ * The rule, for a context with k > 1 streams after n local samples, n a multiple of k (every
+ * stream holds n / k samples, every combine weight is exactly 1 / k): with var, N and M those of
+ * jt_get_variance / jt_get_noise for these samples (a valid estimate is reused, one computed here
+ * serves later calls),
+ *   vmax = (float)((T * M) * (T * M) / (3.0 * N * N))           in double, rounded once
+ * and for every tile t the context traces that is not frozen, lane l = 8 * row + col the pixel
+ * (col, row) of the tile, float32, no FMA:
+ *   v[l] = (var.x + var.y) + var.z for a pixel inside the image, 0 outside
+ *   for off = 32, 16, ..., 1:  v[l] += v[l + off]  (l < off);   V_t = v[0]
+ *   N_t = the tile's pixels inside the image;   the tile freezes iff V_t <= (float)N_t * vmax
+ * i.e. the tile's mean channel variance is at most (T x the image's mean channel value)^2.
+ * Summed over the tiles this is 3 N V <= (T M)^2: if every tile meets it at one call,
+ * jt_get_noise <= T. Freezing is monotone: a frozen tile stays frozen until jt_reset, which
+ * unfreezes every tile. *active_tiles (may be NULL) receives the traced tiles still active.
+ * A frozen pixel's stream means are those of its freeze time. jt_get_image combines them with
+ * the weights of the context's current n, as for every pixel: at any n that is a multiple of k
+ * this is bit for bit the pixel's value when it froze, and the same holds for albedo, normal,
+ * hits and jt_get_variance. jt_get_samples and the sample indices do not change: a pixel still
+ * active at sample s gets exactly the sample s it would get without adaptation. jt_counters
+ * counts what was traced. A tile_share context adapts over its own tiles. jt_describe appends
+ * " adaptive=<active>/<traced tiles>" once jt_adapt has run on the context. A context that never
+ * calls jt_adapt behaves exactly as before.
+ * jt_adapt traces the queued samples first, as every reader does, and leaves image, albedo,
+ * normal, hits, the stream means, the variance and every jt_counters field as a flush alone
+ * would (its launch is not counted). Errors, in this order: JT_ERR_INVALID (naming the argument)
+ * for a NULL ctx or a noise_target that is not finite and > 0, before the context is looked at;
+ * every error of jt_get_variance; JT_ERR_STATE (stating n and k) when n is not a multiple of k.
+ * jt_get_sample_counts (W*H int32; traces the queued samples first): for the pixels of a frozen
+ * tile the n at which it froze, for an active traced tile the context's n, 0 for pixels a tile
+ * share does not trace; all n on a context that never adapted. */
+int jt_adapt(jt_ctx* ctx, double noise_target, int32_t* active_tiles /* may be NULL */);
+int jt_get_sample_counts(jt_ctx* ctx, int32_t* counts /* W*H */);
 
 /* zero accumulators (at once if their device pointers were handed out, else before they are
  * next read or overwritten), samples = 0, queued samples dropped */

@@ -1,6 +1,7 @@
 // jt_context.h — the device context behind include/jtrace.h's jt_ctx and the few functions its
 // pieces share: jt_trace.hip (creation, the sample queue, the getters), jt_multi.hip (the
-// multi-device context), jt_denoise.hip and jt_error.hip (their context halves). Not part of the ABI.
+// multi-device context), jt_denoise.hip, jt_error.hip and jt_adapt.hip (their context halves). Not
+// part of the ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -80,7 +81,18 @@ struct jt_ctx {
     float4* err_var = nullptr;
     float2* err_sums = nullptr;
     double err_noise = 0;
-    bool err_valid = false;  // err_var and err_noise are those of the current running means
+    double err_M = 0;        // the sum of (mu.x + mu.y) + mu.z over the traced pixels behind err_noise
+    bool err_valid = false;  // err_var, err_noise and err_M are those of the current running means
+
+    // ---- adaptive sampling
+    // jt_adapt, jt_get_sample_counts (jt_adapt.hip): per image tile the local sample count at
+    // which it froze (0: active; DAccum::frozen points here) and one word per workgroup of the
+    // adapt launch; allocated (the mask zeroed) by the first jt_adapt, kept across jt_reset, which
+    // zeroes the mask again
+    unsigned* frozen_at = nullptr;
+    unsigned* adapt_words = nullptr;
+    int adapt_active = 0;   // traced tiles still active after the last jt_adapt (all after jt_reset)
+    bool adapted = false;   // jt_adapt has run on this context (jt_describe)
 
     // ---- a multi-device context (jt_create_multi) owns its sub-contexts and reduce state here
     // and uses, of the fields above, only the size, the sample counts, the queue, `failed`,

@@ -142,6 +142,7 @@ int jtc::estimate_error(jt_ctx* c) {
     // N: the traced pixels inside the image (edge tiles are clipped)
     const long long N = jtk::traced_pixels(c->width, c->height, c->P.tile_stride, c->P.tile_offset);
     c->err_noise = M == 0 ? 0.0 : std::sqrt(3.0 * (double)N * V) / M;
+    c->err_M = M;  // jt_adapt's threshold (jt_adapt.hip)
     c->err_valid = true;
     return JT_OK;
 }

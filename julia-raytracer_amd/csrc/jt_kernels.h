@@ -256,7 +256,9 @@ __device__ __forceinline__ float stream_weight(const DParams& P, int s) {
 #define JT_STAMP(x)
 #endif
 
-template <int SAMPLER, int RING, bool OVF, int COUNT, int F, bool NCACHE, bool WIDE>
+// ADAPT: the twin an adapted context launches (jt_adapt, jt_adapt.hip): its hand-out skips the
+// units of frozen tiles. Every other instantiation holds no trace of it.
+template <int SAMPLER, int RING, bool OVF, int COUNT, int F, bool NCACHE, bool WIDE, bool ADAPT = false>
 __device__ __forceinline__ void trace_body_items(const DScene& S0, const DParams& P0, int s_begin, int s_end,
                                                  const DAccum& A, int* stack) {
     const DScene& S = S0;
@@ -348,6 +350,14 @@ __device__ __forceinline__ void trace_body_items(const DScene& S0, const DParams
                     tile = bt0 + (sidx * STRIP + v % h) * gx + v / h;
                 }
                 ut = tile * P.tile_stride + P.tile_offset;
+                // a tile jt_adapt froze takes no more samples: its stream means stay as they are
+                // (ut is wave-uniform: a scalar load and a scalar branch per unit)
+                if constexpr (ADAPT) {
+                    if (JT_A(frozen)[ut]) {
+                        bnext = 64;
+                        continue;
+                    }
+                }
                 bnext = 0;
             }
             const int nneed = lane_count(needm), take = nneed < 64 - bnext ? nneed : 64 - bnext;
@@ -723,6 +733,12 @@ __global__ __launch_bounds__(BLOCK) JT_WAVES_PER_EU void trace_kernel(DScene S, 
     __shared__ int lds_stack[RING * BLOCK];
     trace_body_items<SAMPLER, RING, OVF, COUNT, F, true, WIDE>(S, P, s_begin, s_end, A, lds_stack + threadIdx.x);
 }
+// its twin for an adapted context (A.frozen is set)
+template <int SAMPLER, int RING, bool OVF, int COUNT, int F, bool WIDE>
+__global__ __launch_bounds__(BLOCK) JT_WAVES_PER_EU void trace_kernel_adapt(DScene S, DParams P, int s_begin, int s_end, DAccum A) {
+    __shared__ int lds_stack[RING * BLOCK];
+    trace_body_items<SAMPLER, RING, OVF, COUNT, F, true, WIDE, true>(S, P, s_begin, s_end, A, lds_stack + threadIdx.x);
+}
 
 // LDS mode (small scenes): the workgroup stages the scene blob into LDS once; every node,
 // instance, primitive and shading record is then a ds_read instead of a vector-memory load
@@ -741,11 +757,42 @@ __global__ __launch_bounds__(BLOCK) JT_WAVES_PER_EU_F(F) void trace_kernel_lds(D
     const DScene L = blob_scene(S, blob);
     trace_body_items<SAMPLER, RING, OVF, COUNT, F, false, WIDE>(L, P, s_begin, s_end, A, reinterpret_cast<int*>(dyn_lds) + threadIdx.x);
 }
+// its twin for an adapted context (A.frozen is set): the same staging, the skipping hand-out
+template <int SAMPLER, int RING, bool OVF, int COUNT, int F, bool WIDE>
+__global__ __launch_bounds__(BLOCK) JT_WAVES_PER_EU_F(F) void trace_kernel_lds_adapt(DScene S, DParams P, int s_begin, int s_end, DAccum A) {
+    extern __shared__ uint4 dyn_lds[];
+    // the stack takes the first bytes (lds_stack_bytes), the blob follows
+    uint4* blob = dyn_lds + lds_stack_bytes(OVF, RING, S.stack_need) / 16;
+    for (int k = threadIdx.x; k < S.blob_n16; k += BLOCK) blob[k] = S.blob[k];
+    __syncthreads();
+    if constexpr (node_baked<OVF, false, WIDE, F>()) {
+        bake_nodes(S, blob);
+        __syncthreads();
+    }
+    const DScene L = blob_scene(S, blob);
+    trace_body_items<SAMPLER, RING, OVF, COUNT, F, false, WIDE, true>(L, P, s_begin, s_end, A, reinterpret_cast<int*>(dyn_lds) + threadIdx.x);
+}
+
+// the kernels of a specialisation: the production ones, or their twins for an adapted context
+template <bool ADAPT, int SAMPLER, int RING, bool OVF, int COUNT, int F, bool WIDE>
+constexpr auto kernel_hbm() {
+    if constexpr (ADAPT)
+        return &trace_kernel_adapt<SAMPLER, RING, OVF, COUNT, F, WIDE>;
+    else
+        return &trace_kernel<SAMPLER, RING, OVF, COUNT, F, WIDE>;
+}
+template <bool ADAPT, int SAMPLER, int RING, bool OVF, int COUNT, int F, bool WIDE>
+constexpr auto kernel_lds() {
+    if constexpr (ADAPT)
+        return &trace_kernel_lds_adapt<SAMPLER, RING, OVF, COUNT, F, WIDE>;
+    else
+        return &trace_kernel_lds<SAMPLER, RING, OVF, COUNT, F, WIDE>;
+}
 
 // Persistent launch: as many workgroups as the device holds at once (capped by the number of
 // tiles), each wave then pulls work units until the launch's units are exhausted.
 // LDSK: the specialisation also has an LDS-mode kernel (the large-scene masks run in HBM mode).
-template <int SAMPLER, int RING, bool OVF, int COUNT, int F, bool LDSK, bool WIDE>
+template <int SAMPLER, int RING, bool OVF, int COUNT, int F, bool LDSK, bool WIDE, bool ADAPT>
 hipError_t launch_t(const DScene& S, const DParams& P, int s0, int s1, const DAccum& A, hipStream_t st, int cus) {
     // one wave per work unit (tile, stream slot) at most
     const long long units = (long long)launch_tiles(P) * std::min(s1 - s0, 1 << P.lk);
@@ -756,25 +803,33 @@ hipError_t launch_t(const DScene& S, const DParams& P, int s0, int s1, const DAc
     if constexpr (LDSK) {
         if (S.blob_n16 > 0) {
         const size_t lds = lds_stack_bytes(OVF, RING, S.stack_need) + (size_t)S.blob_n16 * 16;
-        const void* k = (const void*)trace_kernel_lds<SAMPLER, RING, OVF, COUNT, F, WIDE>;
+        constexpr auto kl = kernel_lds<ADAPT, SAMPLER, RING, OVF, COUNT, F, WIDE>();
+        const void* k = (const void*)kl;
         if ((e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) return e;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, BLOCK, lds) != hipSuccess || per_cu < 1) per_cu = 1;
         const int nwg = std::min(want, std::min(per_cu, 8) * cus);  // <= 8 per CU: the overflow area's bound
-        hipLaunchKernelGGL((trace_kernel_lds<SAMPLER, RING, OVF, COUNT, F, WIDE>), dim3(nwg), dim3(BLOCK), lds, st, S, P, s0, s1, A);
+        hipLaunchKernelGGL(kl, dim3(nwg), dim3(BLOCK), lds, st, S, P, s0, s1, A);
         return hipGetLastError();
         }
     }
-    const void* k = (const void*)trace_kernel<SAMPLER, RING, OVF, COUNT, F, WIDE>;
+    constexpr auto kh = kernel_hbm<ADAPT, SAMPLER, RING, OVF, COUNT, F, WIDE>();
+    const void* k = (const void*)kh;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, BLOCK, 0) != hipSuccess || per_cu < 1) per_cu = 1;
     const int nwg = std::min(want, std::min(per_cu, 8) * cus);
-    hipLaunchKernelGGL((trace_kernel<SAMPLER, RING, OVF, COUNT, F, WIDE>), dim3(nwg), dim3(BLOCK), 0, st, S, P, s0, s1, A);
+    hipLaunchKernelGGL(kh, dim3(nwg), dim3(BLOCK), 0, st, S, P, s0, s1, A);
     return hipGetLastError();
 }
 
 template <int ID, int SAMPLER, int COUNT>
 hipError_t launch_cfg(const DScene& S, const DParams& P, int s0, int s1, const DAccum& A, hipStream_t st, int cus) {
     using C = LaunchConfig<ID>;
-    return launch_t<SAMPLER, C::ring, C::ovf, COUNT, C::feat, C::lds, C::wide>(S, P, s0, s1, A, st, cus);
+    return launch_t<SAMPLER, C::ring, C::ovf, COUNT, C::feat, C::lds, C::wide, false>(S, P, s0, s1, A, st, cus);
+}
+// the same configuration's twins for an adapted context (DAccum::frozen set)
+template <int ID, int SAMPLER, int COUNT>
+hipError_t launch_cfg_adapt(const DScene& S, const DParams& P, int s0, int s1, const DAccum& A, hipStream_t st, int cus) {
+    using C = LaunchConfig<ID>;
+    return launch_t<SAMPLER, C::ring, C::ovf, COUNT, C::feat, C::lds, C::wide, true>(S, P, s0, s1, A, st, cus);
 }
 
 }  // namespace jtk

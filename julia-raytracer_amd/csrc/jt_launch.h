@@ -33,6 +33,12 @@ struct DAccum {
     float4* part_alb;
     float4* part_nrm;
     int nslot;  // launch tiles x 64 (the allocation's slots per stream)
+    // adaptive sampling (jt_adapt, jt_adapt.hip): per image tile the local sample count at which
+    // it froze, 0: active. nullptr until the context's first jt_adapt, and always in multi-device
+    // sub-contexts and one-stream chunks; once set, the context launches the configuration's
+    // adaptive twins (launch_cfg_adapt), whose hand-out skips the units of a frozen tile. The
+    // production kernels never read it
+    const unsigned* frozen;
 };
 
 // The kernels' argument layout (trace_kernel, trace_kernel_lds: by-value arguments in this order,
@@ -71,11 +77,20 @@ constexpr int NBANDS = 8, BAND_STRIDE = 16;
 // launch table of jt_trace.hip) refers to jt_kv's symbol and instantiates nothing.
 template <int ID, int SAMPLER, int COUNT>
 hipError_t launch_cfg(const DScene& S, const DParams& P, int s0, int s1, const DAccum& A, hipStream_t st, int cus);
+// the configuration's twins for an adapted context: the same kernels with the frozen-tile skip in
+// the hand-out, compiled in translation units of their own (jt_kv.hip with JT_KV_ADAPT)
+template <int ID, int SAMPLER, int COUNT>
+hipError_t launch_cfg_adapt(const DScene& S, const DParams& P, int s0, int s1, const DAccum& A, hipStream_t st, int cus);
 // explicit instantiation (in jt_kv.hip) of one configuration for both samplers and both counter levels
 #define JT_KV_INSTANTIATE(ID)                                                                                      \
     template hipError_t launch_cfg<ID, 1, 0>(const DScene&, const DParams&, int, int, const DAccum&, hipStream_t, int); \
     template hipError_t launch_cfg<ID, 1, 1>(const DScene&, const DParams&, int, int, const DAccum&, hipStream_t, int); \
     template hipError_t launch_cfg<ID, 2, 0>(const DScene&, const DParams&, int, int, const DAccum&, hipStream_t, int); \
     template hipError_t launch_cfg<ID, 2, 1>(const DScene&, const DParams&, int, int, const DAccum&, hipStream_t, int);
+#define JT_KV_INSTANTIATE_ADAPT(ID)                                                                                      \
+    template hipError_t launch_cfg_adapt<ID, 1, 0>(const DScene&, const DParams&, int, int, const DAccum&, hipStream_t, int); \
+    template hipError_t launch_cfg_adapt<ID, 1, 1>(const DScene&, const DParams&, int, int, const DAccum&, hipStream_t, int); \
+    template hipError_t launch_cfg_adapt<ID, 2, 0>(const DScene&, const DParams&, int, int, const DAccum&, hipStream_t, int); \
+    template hipError_t launch_cfg_adapt<ID, 2, 1>(const DScene&, const DParams&, int, int, const DAccum&, hipStream_t, int);
 
 }  // namespace jtk

@@ -5,8 +5,8 @@
 // scene's kernel configuration in jt_select.h (select_kernel), the trace kernels in jt_kernels.h (instantiated by jt_kv.hip, one translation unit per configuration; this unit
 // sees only their declarations and the argument records, jt_launch.h), the
 // combine and chain kernels in jt_accum.hip, the multi-device context in jt_multi.hip, and the
-// denoiser's and the error estimate's entry points beside their kernels (jt_denoise.hip,
-// jt_error.hip).
+// denoiser's, the error estimate's and adaptive sampling's entry points beside their kernels
+// (jt_denoise.hip, jt_error.hip, jt_adapt.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -30,14 +30,18 @@ using namespace jtc;
 
 namespace {
 // The launch functions of every configuration (jt_kv.hip compiles each in its own translation
-// unit), indexed [KernelChoice::id][sampler - 1][counter level]
+// unit), indexed [KernelChoice::id][sampler - 1][counter level]; `adapt` holds the same
+// configuration's twins for an adapted context (DAccum::frozen set)
 using LaunchFn = hipError_t (*)(const DScene&, const DParams&, int, int, const DAccum&, hipStream_t, int);
 struct LaunchRow {
     LaunchFn fn[2][2];
+    LaunchFn adapt[2][2];
 };
 template <int... ID>
 constexpr std::array<LaunchRow, sizeof...(ID)> launch_table(std::integer_sequence<int, ID...>) {
-    return {{LaunchRow{{{launch_cfg<ID, 1, 0>, launch_cfg<ID, 1, 1>}, {launch_cfg<ID, 2, 0>, launch_cfg<ID, 2, 1>}}}...}};
+    return {{LaunchRow{{{launch_cfg<ID, 1, 0>, launch_cfg<ID, 1, 1>}, {launch_cfg<ID, 2, 0>, launch_cfg<ID, 2, 1>}},
+                       {{launch_cfg_adapt<ID, 1, 0>, launch_cfg_adapt<ID, 1, 1>},
+                        {launch_cfg_adapt<ID, 2, 0>, launch_cfg_adapt<ID, 2, 1>}}}...}};
 }
 constexpr auto LAUNCH = launch_table(std::make_integer_sequence<int, NUM_LAUNCH_CONFIGS>{});
 }  // namespace
@@ -422,6 +426,12 @@ extern "C" int jt_reset(jt_ctx* c) {
     // a failed flush may have left chains queued on stream2 (a complete one ends on `stream`)
     if (c->stream2 && (e = hipStreamSynchronize(c->stream2)) != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
     if ((e = hipMemsetAsync(c->A.counters, 0, 256, c->stream)) != hipSuccess) return hip_fail(e, "hipMemsetAsync");
+    // adaptive sampling (jt_adapt): every tile is active again; the mask's buffer is kept
+    if (c->frozen_at) {
+        if ((e = hipMemsetAsync(c->frozen_at, 0, (size_t)c->tiles * sizeof(unsigned), c->stream)) != hipSuccess)
+            return hip_fail(e, "hipMemsetAsync");
+        c->adapt_active = launch_tiles(c->P);
+    }
     // make_trace_state's zeroed buffers (src/trace.jl:189-213). A context that traces every tile
     // overwrites every pixel in its first launch without reading it (a stream's first sample
     // starts from zero), so they are zeroed only if read before that launch (zero_if_stale); a
@@ -486,7 +496,9 @@ int ensure_chunk(jt_ctx* c) {
 int launch_range(jt_ctx* c, const DParams& P, const DAccum& A, int32_t s0, int32_t s1) {
     hipError_t e = hipMemsetAsync(c->A.work, 0, SCHED_BYTES, c->stream);
     if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync schedule");
-    e = LAUNCH[c->choice.id].fn[c->sampler == JT_SAMPLER_NAIVE ? 1 : 0][c->count ? 1 : 0](c->S, P, s0, s1, A, c->stream, c->cus);
+    const LaunchRow& row = LAUNCH[c->choice.id];
+    const LaunchFn fn = (A.frozen ? row.adapt : row.fn)[c->sampler == JT_SAMPLER_NAIVE ? 1 : 0][c->count ? 1 : 0];
+    e = fn(c->S, P, s0, s1, A, c->stream, c->cus);
     if (e != hipSuccess) return hip_fail(e, "trace kernel launch");
     return JT_OK;
 }
@@ -716,18 +728,21 @@ int jt_describe(const jt_ctx* c, char* buf, int32_t n) {
     char filt[96] = "";
     if (c->P.tile_stride != 1 || k.ring_shortened())
         std::snprintf(filt, sizeof filt, " tile_filter=%d/%d ring_used=%d", c->P.tile_offset, c->P.tile_stride, c->S.ring);
-    char tmp[640];
+    // adaptive sampling, once jt_adapt has run: the traced tiles still active / the traced tiles
+    char adaptive[48] = "";
+    if (c->adapted) std::snprintf(adaptive, sizeof adaptive, " adaptive=%d/%d", c->adapt_active, launch_tiles(c->P));
+    char tmp[704];
     std::snprintf(tmp, sizeof tmp,
                   "kernel=%s<%d,%d,%s,%d,%d,%s> mode=%s scene_lds_bytes=%zu stack_bound=%d lds_ring=%d hbm_overflow=%d "
                   "wait_lanes=%d light_lanes=%d streams=%d tiles=%d block=%d env_alias=%d light_inline=%d "
-                  "traversal=%s%s",
+                  "traversal=%s%s%s",
                   k.lds_scene_bytes ? "trace_kernel_lds" : "trace_kernel", c->sampler == JT_SAMPLER_NAIVE ? 2 : 1,
                   k.ring, k.ovf ? "true" : "false", c->count, k.kmask, k.wide ? "true" : "false",
                   k.lds_scene_bytes ? "lds" : "hbm", k.lds_scene_bytes,
                   k.stack, k.ring, k.ovf ? 1 : 0, c->P.wait_lanes, c->P.light_lanes, 1 << c->lk, c->tiles, BLOCK,
                   c->env_alias ? 1 : 0, c->S.light_inline,
                   k.traversal == JT_TRAVERSAL_REFERENCE ? "reference" : k.traversal == JT_TRAVERSAL_NEAR ? "near" : "wide",
-                  filt);
+                  filt, adaptive);
     std::snprintf(buf, (size_t)n, "%s", tmp);
     return JT_OK;
 }

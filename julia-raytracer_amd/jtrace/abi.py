@@ -301,6 +301,8 @@ def _declare(lib):
                                             C.POINTER(jt_denoise_guided_params), C.c_int32, f32p]
     lib.jt_get_variance.argtypes = [C.c_void_p, f32p]
     lib.jt_get_noise.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+    lib.jt_adapt.argtypes = [C.c_void_p, C.c_double, i32p]
+    lib.jt_get_sample_counts.argtypes = [C.c_void_p, i32p]
     lib.jt_reset.argtypes = [C.c_void_p]
     lib.jt_get_device_buffers.argtypes = [C.c_void_p, C.POINTER(jt_device_buffers)]
     lib.jt_set_counters.argtypes = [C.c_void_p, C.c_int32]
@@ -319,6 +321,7 @@ EXPORTED_SYMBOLS = [
     "jt_get_aovs", "jt_get_counters", "jt_reset", "jt_get_device_buffers", "jt_set_counters", "jt_describe", "jt_synchronize",
     "jt_destroy", "jt_denoise_defaults", "jt_denoise", "jt_get_denoised", "jt_denoise_image",
     "jt_get_variance", "jt_get_noise", "jt_denoise_guided_defaults", "jt_denoise_guided", "jt_denoise_guided_image",
+    "jt_adapt", "jt_get_sample_counts",
 ]
 
 

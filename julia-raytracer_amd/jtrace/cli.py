@@ -6,8 +6,10 @@ image size, camera aspect := W/H), --device, --devices N (one context over GPUs 
 jt_create_multi), --missing (drop|error for incomplete scenes), --traversal (reference|near|wide|auto:
 the BVH traversal, include/jtrace.h jt_traversal), --noise-target / --noise-interval (stop at an
 estimated relative RMS error, jt_get_noise), --error-output (the per-pixel standard error as a
-second image, jt_get_variance) and --denoise-mode (plain|variance: with --denoise true, the filter of
-jt_denoise or the variance-guided one of jt_denoise_guided).
+second image, jt_get_variance), --denoise-mode (plain|variance: with --denoise true, the filter of
+jt_denoise or the variance-guided one of jt_denoise_guided) and --adaptive / --adaptive-start /
+--samples-output (with --noise-target: 8x8 tiles that meet the target take no more samples,
+jt_adapt; the samples per pixel as a third image, jt_get_sample_counts).
 """
 from __future__ import annotations
 
@@ -79,6 +81,14 @@ def _parser() -> argparse.ArgumentParser:
                    help="with --denoise true: plain (jt_denoise, one colour sigma from the sample count) or "
                         "variance (jt_denoise_guided, the per-pixel variance of jt_get_variance as the colour "
                         "tolerance; extension; needs --batch >= 2)")
+    p.add_argument("--adaptive", type=_bool, default=False,
+                   help="with --noise-target: at every noise check freeze the 8x8 tiles that already meet the "
+                        "target (jt_adapt), so later samples go to the noisy tiles (extension)")
+    p.add_argument("--adaptive-start", type=int, default=64,
+                   help="with --adaptive true: no tile freezes before this many samples (extension)")
+    p.add_argument("--samples-output", type=str, default="",
+                   help="also save the samples per pixel (jt_get_sample_counts), grey = count / max count, to "
+                        "this file (extension)")
     return p
 
 
@@ -96,6 +106,11 @@ def _check_error_flags(parser: argparse.ArgumentParser, ns) -> None:
         if used and ns.devices > 1:
             parser.error(f"{flag} is not available with --devices {ns.devices}: the error estimate is per "
                          "device; pass --devices 1")
+    # --adaptive hands --noise-target down to tiles, so it needs one (and with it the rules above)
+    if ns.adaptive and not ns.noise_target > 0:
+        parser.error("--adaptive true needs --noise-target > 0: the tiles freeze against that target")
+    if ns.adaptive_start < 0:
+        parser.error(f"--adaptive-start must be at least 0, got {ns.adaptive_start}")
 
 
 @dataclass
@@ -129,6 +144,9 @@ class Params:
     noise_interval: int = 16
     error_output: str = ""
     denoise_mode: str = "plain"
+    adaptive: bool = False
+    adaptive_start: int = 64
+    samples_output: str = ""
 
 
 def params_from_dict(d: dict) -> Params:

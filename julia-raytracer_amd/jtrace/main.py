@@ -67,6 +67,13 @@ def run(params: Params, out=print) -> dict:
     noise_target = float(getattr(params, "noise_target", 0.0) or 0.0)
     noise_interval = int(getattr(params, "noise_interval", 16))
     error_output = getattr(params, "error_output", "") or ""
+    # --adaptive: a noise check that does not stop the render freezes the tiles that already meet
+    # the target (jt_adapt), from --adaptive-start samples on and where every stream holds the same
+    # number of samples; the stop stays the image's noise
+    adaptive = bool(getattr(params, "adaptive", False))
+    adaptive_start = int(getattr(params, "adaptive_start", 64))
+    samples_output = getattr(params, "samples_output", "") or ""
+    active_tiles = None
     checked = 0
     for _ in range(0, params.samples, params.batch):
         batch_start = time.perf_counter()
@@ -83,6 +90,11 @@ def run(params: Params, out=print) -> dict:
             if noise <= noise_target:
                 out(f"noise target reached at {done}/{params.samples} samples")
                 break
+            if adaptive and done >= adaptive_start and done % state.streams == 0:
+                active_tiles = state.adapt(noise_target)
+                out(f"adaptive: {active_tiles}/{state.adaptive[1]} tiles active at {done} samples")
+                if active_tiles == 0:
+                    break
     render_s = time.perf_counter() - sampling_start
     out(f"rendered in {format_seconds(render_s)} ({render_s:.3f}s)")
     samples_traced = state.samples
@@ -104,10 +116,17 @@ def run(params: Params, out=print) -> dict:
         error[..., 3] = 1.0
         save_image(error_output, error, state.width, state.height)
         out(f"saved error image to {error_output}")
+    if samples_output:  # the samples behind every pixel: grey = count / max count
+        counts = state.sample_counts().astype(np.float32)
+        grey = counts / max(float(counts.max()), 1.0)
+        save_image(samples_output, np.stack([grey, grey, grey, np.ones_like(grey)], axis=-1), state.width, state.height)
+        out(f"saved sample-count image to {samples_output}")
     out(f"total time: {format_seconds(time.perf_counter() - render_start)}")
     counters = state.counters()
     result = {"render_s": render_s, "width": state.width, "height": state.height, "counters": counters,
-              "samples_traced": samples_traced}
+              "samples_traced": samples_traced, "paths": counters["paths"]}
+    if adaptive:  # the traced tiles still active at the last jt_adapt (None: it never ran)
+        result["active_tiles"] = active_tiles
     if noise_target > 0 or error_output:
         result["noise"] = state.noise()  # of the image saved (the last check's value when it stopped the loop)
     state.close()

@@ -11,6 +11,7 @@
     state.denoise_guided() / denoise_guided_image / denoise_guided_defaults (the build's own)
                                                        -> jt_denoise_guided, jt_denoise_guided_image,
                                                        jt_denoise_guided_defaults
+    state.adapt() / state.sample_counts() (the build's own) -> jt_adapt, jt_get_sample_counts
 
 There is no CPU fallback anywhere in this module: every call goes through libjtrace_hip.so.
 """
@@ -187,6 +188,30 @@ class TraceState:
         v = C.c_double()
         abi.check(self.lib, self.lib.jt_get_noise(self.handle, C.byref(v)))
         return v.value
+
+    def adapt(self, noise_target: float) -> int:
+        """jt_adapt: freezes the 8x8 tiles whose error estimate meets the image-level noise target
+        (later trace calls skip them) and returns the traced tiles still active. Needs k > 1
+        streams and a sample count that is a multiple of k (include/jtrace.h)."""
+        n = C.c_int32()
+        abi.check(self.lib, self.lib.jt_adapt(self.handle, float(noise_target), C.byref(n)))
+        return n.value
+
+    @property
+    def adaptive(self):
+        """(active, traced) tiles of jt_describe's adaptive= field; None before the first adapt()."""
+        for tok in self.describe().split():
+            if tok.startswith("adaptive="):
+                a, t = tok.split("=", 1)[1].split("/")
+                return int(a), int(t)
+        return None
+
+    def sample_counts(self) -> np.ndarray:
+        """jt_get_sample_counts: (H, W) int32, the samples behind every pixel: the count at which
+        its tile froze, the context's samples for an active tile, 0 outside a tile share."""
+        out = np.empty((self.height, self.width), np.int32)
+        abi.check(self.lib, self.lib.jt_get_sample_counts(self.handle, out.ctypes.data_as(abi.i32p)))
+        return out
 
     def counters(self) -> dict:
         c = abi.jt_counters()
