@@ -5,8 +5,8 @@
 //
 // One wave per tile over the launch's tile slots, as error_kernel (jt_error.hip) reads them: each
 // lane loads its pixel's variance (16 B, rows of 128 B), the wave sums the channel sums in the
-// order of wave_sum_f, and lane 0 compares and records the sample count for a tile that newly
-// freezes (an ordinary vector store). Each workgroup writes its count of tiles still active as
+// order of wave_sum_f (jt_error.h), and lane 0 compares and records the sample count for a tile
+// that newly freezes (an ordinary vector store). Each workgroup writes its count of tiles still active as
 // one word; the host adds the words. No atomics: the result does not depend on the order the
 // workgroups run in.
 #include <hip/hip_runtime.h>
@@ -25,13 +25,6 @@ namespace jtk {
 using jt::ADAPT_BLOCK;
 using jt::DAdapt;
 
-// error_kernel's wave sum (jt_error.hip): for off = 32, 16, ..., 1: v[l] += v[l + off]
-__device__ __forceinline__ float adapt_wave_sum_f(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;  // lane 0 holds the sum
-}
-
 __global__ __launch_bounds__(ADAPT_BLOCK) void adapt_kernel(DAdapt D) {
     const int g = (int)(blockIdx.x * ADAPT_BLOCK + threadIdx.x);  // < 2^26 + 256 (jt_create's tile limit)
     const bool traced = g < D.tiles * 64;  // wave-uniform: a wave is one launch tile
@@ -46,7 +39,7 @@ __global__ __launch_bounds__(ADAPT_BLOCK) void adapt_kernel(DAdapt D) {
             v = (var.x + var.y) + var.z;
         }
     }
-    const float vt = adapt_wave_sum_f(v);
+    const float vt = wave_sum_f(v);
     const int nt = __popcll(__builtin_amdgcn_ballot_w64(inside));
     __shared__ unsigned wact[ADAPT_BLOCK / 64];
     if ((threadIdx.x & 63) == 0) {

@@ -1,5 +1,6 @@
 // jt_error.h — the per-pixel error estimate's launch and its context entry; the kernel and the
-// context's half (jt_get_variance, jt_get_noise) are in jt_error.hip. Not part of the ABI.
+// context's half (jt_get_variance, jt_get_noise) are in jt_error.hip. Not part of the ABI; only
+// .hip units include it (wave_sum_f is device code).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -34,6 +35,18 @@ inline int error_blocks(int tiles) { return (int)(((long long)tiles * 64 + ERR_B
 hipError_t error_launch(hipStream_t stream, const DError& E);
 
 }  // namespace jt
+
+namespace jtk {
+
+// the wave's sum in lane 0, in a fixed order: for off = 32, 16, ..., 1: v[l] += v[l + off]
+// (error_kernel's sums and adapt_kernel's tile sums, jt_adapt.hip; restated in tests/adapt_ref.py)
+__device__ __forceinline__ float wave_sum_f(float v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    return v;  // lane 0 holds the sum
+}
+
+}  // namespace jtk
 
 struct jt_ctx;
 

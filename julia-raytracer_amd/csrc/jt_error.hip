@@ -24,12 +24,6 @@ namespace jtk {
 using jt::DError;
 using jt::ERR_BLOCK;
 
-__device__ __forceinline__ float wave_sum_f(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;  // lane 0 holds the sum
-}
-
 __global__ __launch_bounds__(ERR_BLOCK) void error_kernel(DError E) {
     const int g = (int)(blockIdx.x * ERR_BLOCK + threadIdx.x);  // < 2^26 + 256 (jt_create's tile limit)
     // slots past the launch's tiles and pixels of an edge tile outside the image add 0 to the sums

@@ -19,8 +19,9 @@
 //
 // Build: every kernel configuration (CONFIGS, jt_select.h) is instantiated in its own
 // translation unit (jt_kv.hip, compiled once per configuration, the only file that includes this
-// header) so the kernels compile in parallel; the host context (jt_trace.hip) only declares them
-// (jt_launch.h). The records the kernels read are declared in jt_records.h (through jt_device.h)
+// header) so the kernels compile in parallel, and once more with the kernels' last template
+// argument ADAPT set, for the contexts that jt_adapt has touched; the host context
+// (jt_trace.hip) only declares them (jt_launch.h). The records the kernels read are declared in jt_records.h (through jt_device.h)
 // and written on the host by jt_layout.cpp.
 #pragma once
 
@@ -728,22 +729,19 @@ __device__ __forceinline__ void bake_nodes(const DScene& S, uint4* blob) {
 }
 
 // HBM mode: the scene is read from global memory (L2/MALL-resident); stack in static LDS.
-template <int SAMPLER, int RING, bool OVF, int COUNT, int F, bool WIDE>
+// ADAPT (both kernels): the instance an adapted context launches (A.frozen is set), passed on to
+// trace_body_items. A template parameter here leaves every instance's ISA as it is; moving a
+// kernel's text into a shared device function does not.
+template <int SAMPLER, int RING, bool OVF, int COUNT, int F, bool WIDE, bool ADAPT>
 __global__ __launch_bounds__(BLOCK) JT_WAVES_PER_EU void trace_kernel(DScene S, DParams P, int s_begin, int s_end, DAccum A) {
     __shared__ int lds_stack[RING * BLOCK];
-    trace_body_items<SAMPLER, RING, OVF, COUNT, F, true, WIDE>(S, P, s_begin, s_end, A, lds_stack + threadIdx.x);
-}
-// its twin for an adapted context (A.frozen is set)
-template <int SAMPLER, int RING, bool OVF, int COUNT, int F, bool WIDE>
-__global__ __launch_bounds__(BLOCK) JT_WAVES_PER_EU void trace_kernel_adapt(DScene S, DParams P, int s_begin, int s_end, DAccum A) {
-    __shared__ int lds_stack[RING * BLOCK];
-    trace_body_items<SAMPLER, RING, OVF, COUNT, F, true, WIDE, true>(S, P, s_begin, s_end, A, lds_stack + threadIdx.x);
+    trace_body_items<SAMPLER, RING, OVF, COUNT, F, true, WIDE, ADAPT>(S, P, s_begin, s_end, A, lds_stack + threadIdx.x);
 }
 
 // LDS mode (small scenes): the workgroup stages the scene blob into LDS once; every node,
 // instance, primitive and shading record is then a ds_read instead of a vector-memory load
 // through the TA/TD path (the measured limiter of the HBM-mode kernel).
-template <int SAMPLER, int RING, bool OVF, int COUNT, int F, bool WIDE>
+template <int SAMPLER, int RING, bool OVF, int COUNT, int F, bool WIDE, bool ADAPT>
 __global__ __launch_bounds__(BLOCK) JT_WAVES_PER_EU_F(F) void trace_kernel_lds(DScene S, DParams P, int s_begin, int s_end, DAccum A) {
     extern __shared__ uint4 dyn_lds[];
     // the stack takes the first bytes (lds_stack_bytes), the blob follows
@@ -755,38 +753,7 @@ __global__ __launch_bounds__(BLOCK) JT_WAVES_PER_EU_F(F) void trace_kernel_lds(D
         __syncthreads();
     }
     const DScene L = blob_scene(S, blob);
-    trace_body_items<SAMPLER, RING, OVF, COUNT, F, false, WIDE>(L, P, s_begin, s_end, A, reinterpret_cast<int*>(dyn_lds) + threadIdx.x);
-}
-// its twin for an adapted context (A.frozen is set): the same staging, the skipping hand-out
-template <int SAMPLER, int RING, bool OVF, int COUNT, int F, bool WIDE>
-__global__ __launch_bounds__(BLOCK) JT_WAVES_PER_EU_F(F) void trace_kernel_lds_adapt(DScene S, DParams P, int s_begin, int s_end, DAccum A) {
-    extern __shared__ uint4 dyn_lds[];
-    // the stack takes the first bytes (lds_stack_bytes), the blob follows
-    uint4* blob = dyn_lds + lds_stack_bytes(OVF, RING, S.stack_need) / 16;
-    for (int k = threadIdx.x; k < S.blob_n16; k += BLOCK) blob[k] = S.blob[k];
-    __syncthreads();
-    if constexpr (node_baked<OVF, false, WIDE, F>()) {
-        bake_nodes(S, blob);
-        __syncthreads();
-    }
-    const DScene L = blob_scene(S, blob);
-    trace_body_items<SAMPLER, RING, OVF, COUNT, F, false, WIDE, true>(L, P, s_begin, s_end, A, reinterpret_cast<int*>(dyn_lds) + threadIdx.x);
-}
-
-// the kernels of a specialisation: the production ones, or their twins for an adapted context
-template <bool ADAPT, int SAMPLER, int RING, bool OVF, int COUNT, int F, bool WIDE>
-constexpr auto kernel_hbm() {
-    if constexpr (ADAPT)
-        return &trace_kernel_adapt<SAMPLER, RING, OVF, COUNT, F, WIDE>;
-    else
-        return &trace_kernel<SAMPLER, RING, OVF, COUNT, F, WIDE>;
-}
-template <bool ADAPT, int SAMPLER, int RING, bool OVF, int COUNT, int F, bool WIDE>
-constexpr auto kernel_lds() {
-    if constexpr (ADAPT)
-        return &trace_kernel_lds_adapt<SAMPLER, RING, OVF, COUNT, F, WIDE>;
-    else
-        return &trace_kernel_lds<SAMPLER, RING, OVF, COUNT, F, WIDE>;
+    trace_body_items<SAMPLER, RING, OVF, COUNT, F, false, WIDE, ADAPT>(L, P, s_begin, s_end, A, reinterpret_cast<int*>(dyn_lds) + threadIdx.x);
 }
 
 // Persistent launch: as many workgroups as the device holds at once (capped by the number of
@@ -803,7 +770,7 @@ hipError_t launch_t(const DScene& S, const DParams& P, int s0, int s1, const DAc
     if constexpr (LDSK) {
         if (S.blob_n16 > 0) {
         const size_t lds = lds_stack_bytes(OVF, RING, S.stack_need) + (size_t)S.blob_n16 * 16;
-        constexpr auto kl = kernel_lds<ADAPT, SAMPLER, RING, OVF, COUNT, F, WIDE>();
+        constexpr auto kl = &trace_kernel_lds<SAMPLER, RING, OVF, COUNT, F, WIDE, ADAPT>;
         const void* k = (const void*)kl;
         if ((e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) return e;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, BLOCK, lds) != hipSuccess || per_cu < 1) per_cu = 1;
@@ -812,7 +779,7 @@ hipError_t launch_t(const DScene& S, const DParams& P, int s0, int s1, const DAc
         return hipGetLastError();
         }
     }
-    constexpr auto kh = kernel_hbm<ADAPT, SAMPLER, RING, OVF, COUNT, F, WIDE>();
+    constexpr auto kh = &trace_kernel<SAMPLER, RING, OVF, COUNT, F, WIDE, ADAPT>;
     const void* k = (const void*)kh;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, BLOCK, 0) != hipSuccess || per_cu < 1) per_cu = 1;
     const int nwg = std::min(want, std::min(per_cu, 8) * cus);
@@ -820,16 +787,10 @@ hipError_t launch_t(const DScene& S, const DParams& P, int s0, int s1, const DAc
     return hipGetLastError();
 }
 
-template <int ID, int SAMPLER, int COUNT>
+template <int ID, int SAMPLER, int COUNT, bool ADAPT>
 hipError_t launch_cfg(const DScene& S, const DParams& P, int s0, int s1, const DAccum& A, hipStream_t st, int cus) {
     using C = LaunchConfig<ID>;
-    return launch_t<SAMPLER, C::ring, C::ovf, COUNT, C::feat, C::lds, C::wide, false>(S, P, s0, s1, A, st, cus);
-}
-// the same configuration's twins for an adapted context (DAccum::frozen set)
-template <int ID, int SAMPLER, int COUNT>
-hipError_t launch_cfg_adapt(const DScene& S, const DParams& P, int s0, int s1, const DAccum& A, hipStream_t st, int cus) {
-    using C = LaunchConfig<ID>;
-    return launch_t<SAMPLER, C::ring, C::ovf, COUNT, C::feat, C::lds, C::wide, true>(S, P, s0, s1, A, st, cus);
+    return launch_t<SAMPLER, C::ring, C::ovf, COUNT, C::feat, C::lds, C::wide, ADAPT>(S, P, s0, s1, A, st, cus);
 }
 
 }  // namespace jtk

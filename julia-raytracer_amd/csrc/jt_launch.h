@@ -36,8 +36,8 @@ struct DAccum {
     // adaptive sampling (jt_adapt, jt_adapt.hip): per image tile the local sample count at which
     // it froze, 0: active. nullptr until the context's first jt_adapt, and always in multi-device
     // sub-contexts and one-stream chunks; once set, the context launches the configuration's
-    // adaptive twins (launch_cfg_adapt), whose hand-out skips the units of a frozen tile. The
-    // production kernels never read it
+    // ADAPT instances (launch_cfg<..., true>), whose hand-out skips the units of a frozen tile.
+    // The production instances never read it
     const unsigned* frozen;
 };
 
@@ -75,22 +75,14 @@ constexpr int NBANDS = 8, BAND_STRIDE = 16;
 // One configuration (LaunchConfig<ID>, jt_select.h): defined in jt_kernels.h, instantiated by
 // jt_kv.hip. Every other unit sees this declaration only, so naming a specialisation there (the
 // launch table of jt_trace.hip) refers to jt_kv's symbol and instantiates nothing.
-template <int ID, int SAMPLER, int COUNT>
+// ADAPT: the configuration's kernels with the frozen-tile skip in the hand-out, for an adapted
+// context (DAccum::frozen); jt_kv.hip instantiates them in translation units of their own.
+template <int ID, int SAMPLER, int COUNT, bool ADAPT>
 hipError_t launch_cfg(const DScene& S, const DParams& P, int s0, int s1, const DAccum& A, hipStream_t st, int cus);
-// the configuration's twins for an adapted context: the same kernels with the frozen-tile skip in
-// the hand-out, compiled in translation units of their own (jt_kv.hip with JT_KV_ADAPT)
-template <int ID, int SAMPLER, int COUNT>
-hipError_t launch_cfg_adapt(const DScene& S, const DParams& P, int s0, int s1, const DAccum& A, hipStream_t st, int cus);
 // explicit instantiation (in jt_kv.hip) of one configuration for both samplers and both counter levels
-#define JT_KV_INSTANTIATE(ID)                                                                                      \
-    template hipError_t launch_cfg<ID, 1, 0>(const DScene&, const DParams&, int, int, const DAccum&, hipStream_t, int); \
-    template hipError_t launch_cfg<ID, 1, 1>(const DScene&, const DParams&, int, int, const DAccum&, hipStream_t, int); \
-    template hipError_t launch_cfg<ID, 2, 0>(const DScene&, const DParams&, int, int, const DAccum&, hipStream_t, int); \
-    template hipError_t launch_cfg<ID, 2, 1>(const DScene&, const DParams&, int, int, const DAccum&, hipStream_t, int);
-#define JT_KV_INSTANTIATE_ADAPT(ID)                                                                                      \
-    template hipError_t launch_cfg_adapt<ID, 1, 0>(const DScene&, const DParams&, int, int, const DAccum&, hipStream_t, int); \
-    template hipError_t launch_cfg_adapt<ID, 1, 1>(const DScene&, const DParams&, int, int, const DAccum&, hipStream_t, int); \
-    template hipError_t launch_cfg_adapt<ID, 2, 0>(const DScene&, const DParams&, int, int, const DAccum&, hipStream_t, int); \
-    template hipError_t launch_cfg_adapt<ID, 2, 1>(const DScene&, const DParams&, int, int, const DAccum&, hipStream_t, int);
+#define JT_KV_INSTANCE(ID, SAMPLER, COUNT, ADAPT) \
+    template hipError_t launch_cfg<ID, SAMPLER, COUNT, ADAPT>(const DScene&, const DParams&, int, int, const DAccum&, hipStream_t, int);
+#define JT_KV_INSTANTIATE(ID, ADAPT) \
+    JT_KV_INSTANCE(ID, 1, 0, ADAPT) JT_KV_INSTANCE(ID, 1, 1, ADAPT) JT_KV_INSTANCE(ID, 2, 0, ADAPT) JT_KV_INSTANCE(ID, 2, 1, ADAPT)
 
 }  // namespace jtk

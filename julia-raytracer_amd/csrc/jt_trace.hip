@@ -30,18 +30,19 @@ using namespace jtc;
 
 namespace {
 // The launch functions of every configuration (jt_kv.hip compiles each in its own translation
-// unit), indexed [KernelChoice::id][sampler - 1][counter level]; `adapt` holds the same
-// configuration's twins for an adapted context (DAccum::frozen set)
+// unit), indexed [KernelChoice::id] and then [adapted][sampler - 1][counter level]; adapted: the
+// context has a frozen-tile mask (DAccum::frozen set)
 using LaunchFn = hipError_t (*)(const DScene&, const DParams&, int, int, const DAccum&, hipStream_t, int);
 struct LaunchRow {
-    LaunchFn fn[2][2];
-    LaunchFn adapt[2][2];
+    LaunchFn fn[2][2][2];
 };
+template <int ID, bool... ADAPT>
+constexpr LaunchRow launch_row(std::integer_sequence<bool, ADAPT...>) {
+    return {{{{launch_cfg<ID, 1, 0, ADAPT>, launch_cfg<ID, 1, 1, ADAPT>}, {launch_cfg<ID, 2, 0, ADAPT>, launch_cfg<ID, 2, 1, ADAPT>}}...}};
+}
 template <int... ID>
 constexpr std::array<LaunchRow, sizeof...(ID)> launch_table(std::integer_sequence<int, ID...>) {
-    return {{LaunchRow{{{launch_cfg<ID, 1, 0>, launch_cfg<ID, 1, 1>}, {launch_cfg<ID, 2, 0>, launch_cfg<ID, 2, 1>}},
-                       {{launch_cfg_adapt<ID, 1, 0>, launch_cfg_adapt<ID, 1, 1>},
-                        {launch_cfg_adapt<ID, 2, 0>, launch_cfg_adapt<ID, 2, 1>}}}...}};
+    return {{launch_row<ID>(std::integer_sequence<bool, false, true>{})...}};
 }
 constexpr auto LAUNCH = launch_table(std::make_integer_sequence<int, NUM_LAUNCH_CONFIGS>{});
 }  // namespace
@@ -496,8 +497,7 @@ int ensure_chunk(jt_ctx* c) {
 int launch_range(jt_ctx* c, const DParams& P, const DAccum& A, int32_t s0, int32_t s1) {
     hipError_t e = hipMemsetAsync(c->A.work, 0, SCHED_BYTES, c->stream);
     if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync schedule");
-    const LaunchRow& row = LAUNCH[c->choice.id];
-    const LaunchFn fn = (A.frozen ? row.adapt : row.fn)[c->sampler == JT_SAMPLER_NAIVE ? 1 : 0][c->count ? 1 : 0];
+    const LaunchFn fn = LAUNCH[c->choice.id].fn[A.frozen != nullptr][c->sampler == JT_SAMPLER_NAIVE ? 1 : 0][c->count ? 1 : 0];
     e = fn(c->S, P, s0, s1, A, c->stream, c->cus);
     if (e != hipSuccess) return hip_fail(e, "trace kernel launch");
     return JT_OK;

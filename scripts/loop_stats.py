@@ -1,11 +1,12 @@
 """Instruction mix of the traversal loop (the Depth=2 loop holding the s_bcnt1 ballots) of one
-kernel in a hipcc -S listing. usage: python scripts/loop_stats.py <file.s> [kernel-prefix]"""
+kernel in a hipcc -S listing (default: the headline's, configuration 0's LDS-mode path kernel).
+usage: python scripts/loop_stats.py <file.s> [kernel-prefix]"""
 import collections
 import re
 import sys
 
 path = sys.argv[1]
-name = sys.argv[2] if len(sys.argv) > 2 else "_ZN12_GLOBAL__N_116trace_kernel_ldsILi1ELi16ELi0E"
+name = sys.argv[2] if len(sys.argv) > 2 else "_ZN3jtk16trace_kernel_ldsILi1ELi16ELb0ELi0ELi8192ELb0ELb0E"
 s = open(path).read().split("\n")
 start = next(i for i, l in enumerate(s) if l.startswith(name))
 end = next(i for i in range(start, len(s)) if s[i].startswith(".Lfunc_end"))

@@ -1,7 +1,8 @@
 """Summarise rocprofv3 --pmc csv passes: per-dispatch averages for the trace kernel.
 
 usage: python scripts/pmc_summary.py <dir with p*/ passes> [kernel-name substring, default: the
-production (COUNT=0) instances, i.e. names containing "trace_kernel" and not ", 1, " as COUNT]"""
+production instances, i.e. names containing "trace_kernel" with COUNT (4th template argument) 0
+and ADAPT (7th) false]"""
 import collections
 import csv
 import glob
@@ -19,7 +20,8 @@ def match(name):
     targs = name[name.index("<") + 1:name.index(">")].split(",")
     if "trace_kernel_wf" in name:  # <SAMPLER, COUNT, F, LDSM>
         return targs[1].strip() == "0"
-    return len(targs) >= 4 and targs[3].strip() == "0"  # COUNT=0: the timed kernel, not the counting pass
+    # COUNT=0: the timed kernel, not the counting pass; not an adapted context's instance
+    return len(targs) >= 4 and targs[3].strip() == "0" and (len(targs) < 7 or targs[6].strip() == "false")
 agg = collections.defaultdict(list)
 meta = {}
 for f in sorted(glob.glob(f"{root}/p*/p*_counter_collection.csv")):

@@ -2,7 +2,8 @@
 VGPRs, scratch bytes per lane, occupancy, per launch configuration (csrc/jt_launch.h
 LaunchConfig), and the scratch stores inside the kernel's loops (spill write-back executed per
 path or per query, not once per launch: the WRITE traffic the roofline records show). Compiles
-csrc/jt_kv.hip once per configuration with -Rpass-analysis and once to ISA.
+csrc/jt_kv.hip once per configuration with -Rpass-analysis and once to ISA. With -DJT_KV_ADAPT=1
+among the extra flags the units hold the kernels' ADAPT instances, and those are the rows.
 usage: python scripts/resource_usage.py [extra hipcc flags...]"""
 import re
 import subprocess
@@ -61,11 +62,12 @@ def main():
     extra = sys.argv[1:]
     with ThreadPoolExecutor(7) as ex:
         res = list(ex.map(lambda v: usage(v, extra), range(len(NAMES))))
+    adapt = "1" if "-DJT_KV_ADAPT=1" in extra else "0"
     print(f"{'config':22} {'kernel':16} {'sampler':7} {'VGPRs':>5} {'spill':>5} {'scratch':>7} {'occ':>3} {'loop stores':>11}")
     for v, rows in res:
         for r in rows:
-            m = re.search(r"(trace_kernel\w*)ILi(\d)ELi(\d+)ELb(\d)ELi(\d)ELi(\d+)ELb(\d)E", r["name"])
-            if not m or m.group(5) != "0":
+            m = re.search(r"(trace_kernel\w*)ILi(\d)ELi(\d+)ELb(\d)ELi(\d)ELi(\d+)ELb(\d)ELb(\d)E", r["name"])
+            if not m or m.group(5) != "0" or m.group(8) != adapt:
                 continue
             print(f"{NAMES[v]:22} {m.group(1):16} {m.group(2):7} {r.get('VGPRs', 0):5} {r.get('VGPRs Spill', 0):5} "
                   f"{r.get('ScratchSize [bytes/lane]', 0):7} {r.get('Occupancy [waves/SIMD]', 0):3} {r['loop_stores']:11}")

@@ -102,7 +102,14 @@ def source_hash(root=ROOT):
 
 CUS = 256
 XCDS = 8
-KERNEL_RE = re.compile(r"(trace_kernel\w*<\d+, \d+, (?:true|false), 0, \d+, (?:true|false)>)")  # <.., WIDE>
+# A production instance in the profiler's demangled form: COUNT (4th template argument) 0 and ADAPT
+# (7th, last) false. Group 1 with ">" is the record's name, the six-argument form of jt_describe.
+KERNEL_RE = re.compile(r"(trace_kernel\w*<\d+, \d+, (?:true|false), 0, \d+, (?:true|false)), false>")
+
+
+def profiler_name(kernel):
+    """The profiler's seven-argument name of the production instance a record names."""
+    return kernel[:-1] + ", false>"
 
 
 def timed_kernel(stats_csv):
@@ -110,20 +117,22 @@ def timed_kernel(stats_csv):
     for r in csv.DictReader(open(stats_csv)):
         m = KERNEL_RE.search(r["Name"])
         if m and (best is None or float(r["TotalDurationNs"]) > best[0]):
-            best = (float(r["TotalDurationNs"]), m.group(1), float(r["AverageNs"]), int(r["Calls"]))
+            best = (float(r["TotalDurationNs"]), m.group(1) + ">", float(r["AverageNs"]), int(r["Calls"]))
     if best is None:
-        raise SystemExit(f"no COUNT=0 trace kernel in {stats_csv}")
+        raise SystemExit(f"no production COUNT=0 trace kernel in {stats_csv}")
     return best[1], best[2], best[3]
 
 
 def counter_means(d, kernel):
-    """Per-dispatch sums of every counter of `kernel` (summed over the counter's dimensions),
-    averaged over dispatches; plus the mean dispatch duration of those runs."""
+    """Per-dispatch sums of every counter of `kernel` (a record's name; rows are matched by the
+    profiler's full name, so its ADAPT instance is not counted in), summed over the counter's dimensions and averaged over dispatches; plus the mean dispatch
+    duration of those runs."""
+    full = profiler_name(kernel)
     per = {}
     durs = {}
     for f in glob.glob(f"{d}/**/*counter_collection.csv", recursive=True):
         for r in csv.DictReader(open(f)):
-            if kernel not in r["Kernel_Name"].replace("(anonymous namespace)::", ""):
+            if full not in r["Kernel_Name"]:
                 continue
             key = (f, r["Dispatch_Id"])
             per.setdefault(r["Counter_Name"], {}).setdefault(key, 0.0)

@@ -1,17 +1,14 @@
-"""Name of the timed trace kernel in a rocprofv3 kernel_stats.csv: the COUNT=0 instance (4th
-template argument) with the most total time, as "trace_kernel_lds<1, 16, false, 0, 0, false>".
+"""Name of the timed trace kernel in a rocprofv3 kernel_stats.csv: the production instance (COUNT,
+the 4th template argument, 0; ADAPT, the last, false) with the most total time, in the
+six-argument form of jt_describe and the roofline records, as
+"trace_kernel_lds<1, 16, false, 0, 0, false>" (roofline.timed_kernel).
 
 usage: python scripts/timed_kernel.py <kt_kernel_stats.csv>
 """
-import csv
-import re
 import sys
+from pathlib import Path
 
-best = None
-for r in csv.DictReader(open(sys.argv[1])):
-    m = re.search(r"(trace_kernel\w*<\d+, \d+, (?:true|false), 0, \d+, (?:true|false)>)", r["Name"])
-    if m and (best is None or float(r["TotalDurationNs"]) > best[0]):
-        best = (float(r["TotalDurationNs"]), m.group(1))
-if best is None:
-    raise SystemExit("no COUNT=0 trace kernel in " + sys.argv[1])
-print(best[1])
+sys.path.insert(0, str(Path(__file__).resolve().parent))
+from roofline import timed_kernel  # noqa: E402
+
+print(timed_kernel(sys.argv[1])[0])

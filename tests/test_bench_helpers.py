@@ -33,3 +33,30 @@ def test_committed_records_match_only_their_build(name):
     assert found is not None and found["build"] == rec["build"] and src.startswith("profiles/")
     assert bench.roofline_record(rec["workload"], rec["kernel"], "0" * 16) == (None, None)
     assert bench.roofline_record(rec["workload"] + " x", rec["kernel"], rec["build"]) == (None, None)
+
+
+def test_timed_kernel_is_the_production_instance(tmp_path, monkeypatch):
+    """The profiler names a trace kernel with seven template arguments, the last one ADAPT. The
+    timed kernel is the production instance (COUNT 0, ADAPT false) whatever time an adapted
+    context's instance or a counting instance took, and its record carries jt_describe's
+    six-argument name, by which bench.py finds it."""
+    sys.path.insert(0, str(ROOT / "scripts"))
+    import roofline
+
+    args = "(jtd::DScene, jtd::DParams, int, int, jtk::DAccum)"
+    stats = tmp_path / "kernel_stats.csv"
+    stats.write_text(
+        '"Name","Calls","TotalDurationNs","AverageNs","Percentage","MinNs","MaxNs","StdDev"\n'
+        f'"void jtk::trace_kernel_lds<1, 16, false, 0, 8192, false, false>{args}",2,2000,1000.0,20.0,900,1100,100.0\n'
+        f'"void jtk::trace_kernel_lds<1, 16, false, 0, 8192, false, true>{args}",3,6000,2000.0,60.0,1900,2100,100.0\n'
+        f'"void jtk::trace_kernel_lds<1, 16, false, 1, 8192, false, false>{args}",1,3000,3000.0,30.0,3000,3000,0.0\n')
+    kernel, avg_ns, calls = roofline.timed_kernel(str(stats))
+    assert (kernel, avg_ns, calls) == ("trace_kernel_lds<1, 16, false, 0, 8192, false>", 1000.0, 2)
+
+    rec = {"workload": "w", "kernel": kernel, "build": "0123456789abcdef"}
+    (tmp_path / "profiles" / "x_roofline").mkdir(parents=True)
+    (tmp_path / "profiles" / "x_roofline" / "w.json").write_text(json.dumps(rec))
+    monkeypatch.setattr(bench, "ROOT", tmp_path)
+    desc = "kernel=trace_kernel_lds<1,16,false,0,8192,false> mode=lds scene_lds_bytes=7648"
+    found, src = bench.roofline_record("w", desc.split()[0].split("=", 1)[1], rec["build"])
+    assert found == rec and src == "profiles/x_roofline/w.json"

@@ -5,7 +5,8 @@ that later samples skip exactly the frozen tiles and leave every other pixel to 
 unadapted render, the state rules, tile shares, jt_describe and the CLI's --adaptive.
 
 Cornellbox, traversal near, seed 0x5EED (conftest.make_params). The shapes are the error tests'
-own: 44x36 (partial edge tiles, 30 tiles: more than one workgroup) and 32x32."""
+own: 44x36 (partial edge tiles, 30 tiles: more than one workgroup) and 32x32; 24x20 for the run
+through the other kernels' ADAPT instances (HBM mode, the wide traversal, the stack overflow)."""
 import ctypes as C
 
 import numpy as np
@@ -146,6 +147,36 @@ def test_adapt_at_sixteen_streams(gpu, abi, lib, cornell_abi, options, sampler):
     st, _, frozen, _, _, _ = _adapt_and_continue(abi, lib, cornell_abi, f"32x32 k=16 sampler {sampler}", 32, 64,
                                                  width=32, height=32, samples=64, batch=32, sampler=sampler)
     assert st.streams == 16 and frozen.any() and not frozen.all()
+    st.close()
+
+
+# ---- 2b. other kernels' ADAPT instances ---------------------------------------------------------
+# (options, make_params arguments, the tokens jt_describe must show): the HBM-mode kernel of
+# configuration 0, that of its wide twin (configuration 8), and the LDS-mode kernel whose stack
+# overflows into HBM (configuration 5, OVF)
+KERNEL_CASES = {
+    "hbm": ({"lds_scene": "0"}, {}, ("mode=hbm", "traversal=near")),
+    "hbm-wide": ({"lds_scene": "0"}, {"traversal": "wide"}, ("mode=hbm", "traversal=wide")),
+    "lds-overflow": ({"test_lds_ring": "2"}, {}, ("mode=lds", "hbm_overflow=1", "ring_used=2")),
+}
+
+
+@pytest.mark.parametrize("case", list(KERNEL_CASES))
+def test_adapt_in_other_kernels(gpu, abi, lib, cornell_abi, options, case):
+    """24x20 (9 tiles, a partial bottom row, three adapt workgroups), k = 4: adapt at 8 with the
+    median target, trace to 16; every check of the helper, bit for bit against an unadapted
+    context under the same options."""
+    opts, params, tokens = KERNEL_CASES[case]
+    options("streams", "4")
+    for name, value in opts.items():
+        options(name, value)
+    st, _, frozen, _, _, _ = _adapt_and_continue(abi, lib, cornell_abi, case, 8, 16,
+                                                 width=24, height=20, samples=32, **params)
+    desc = f" {st.describe()} "
+    print(f"{case}: {frozen.sum()} of {frozen.size} tiles frozen; {desc.strip()}")
+    for token in tokens:
+        assert f" {token} " in desc, (token, desc)
+    assert frozen.any() and not frozen.all()
     st.close()
 
 
