@@ -2525,3 +2525,137 @@ void or_inverse_frame(const float* frame, int32_t non_rigid, float* out) {
 void or_srgb_to_rgb(const uint8_t* bytes, int32_t n, float* out) {
     for (int i = 0; i < n; i++) out[i] = srgb_to_rgb1(bytes[i] / 255.0f);
 }
+
+/* ---- single-primitive probes (tests/test_primitives_host.py, tests/test_gpu_primitives.py): the
+ * static functions above, one op per primitive, under the ids and the per-lane record widths of
+ * the device probe library (tests/probe/jt_probe.hip). An op reads nin floats per lane and writes
+ * nout (booleans as 0.0f / 1.0f). The two op tables are compared by a CPU test. */
+enum {
+    OP_SINCOS = 0, OP_DISK, OP_ATAN, OP_ATAN2, OP_ACOS, OP_LOG, OP_EXP, OP_MINMAX, OP_RCP, OP_BBOX, OP_TRIANGLE,
+    OP_QUAD, OP_BSDF, OP_PARTS, OP_VOLUME, OP_COUNT
+};
+static const struct { const char* name; int nin, nout; } probe_ops[OP_COUNT] = {
+    {"sincos", 1, 6}, {"disk", 1, 4},       {"atan", 1, 7},   {"atan2", 2, 1}, {"acos", 1, 1},
+    {"log", 1, 1},    {"exp", 1, 1},        {"minmax", 3, 6}, {"rcp", 1, 1},   {"bbox", 14, 1},
+    {"triangle", 17, 12}, {"quad", 20, 4},  {"bsdf", 18, 18}, {"parts", 18, 24}, {"volume", 19, 12},
+};
+int or_probe_count(void) { return OP_COUNT; }
+const char* or_probe_name(int op) { return op >= 0 && op < OP_COUNT ? probe_ops[op].name : NULL; }
+int or_probe_nin(int op) { return op >= 0 && op < OP_COUNT ? probe_ops[op].nin : -1; }
+int or_probe_nout(int op) { return op >= 0 && op < OP_COUNT ? probe_ops[op].nout : -1; }
+
+static inline v3 pld3(const float* x) { return V3(x[0], x[1], x[2]); }
+static inline void pst3(float* y, v3 a) { y[0] = a.x; y[1] = a.y; y[2] = a.z; }
+static inline void pst_isec(float* y, prim_isec p) {
+    y[0] = p.uv.x; y[1] = p.uv.y; y[2] = p.distance; y[3] = p.hit ? 1.0f : 0.0f;
+}
+static inline void pst_doubles(float* y, double s, double c) { /* lo, hi words of each, bit copies */
+    memcpy(y, &s, 8);
+    memcpy(y + 2, &c, 8);
+}
+static material_point probe_material(const float* x) {
+    material_point m;
+    memset(&m, 0, sizeof(m));
+    m.type = (int)x[0];
+    m.color = pld3(x + 1);
+    m.ior = x[4];
+    m.roughness = x[5];
+    return m;
+}
+static void probe1(int op, const float* x, float* y) {
+    switch (op) {
+        /* slots 2.. : the doubles the device rounds its results from (its own algorithm's; a GPU
+         * test compares them with that algorithm restated). Here: this C library's, same layout. */
+        case OP_SINCOS: y[0] = jl_sin(x[0]); y[1] = jl_cos(x[0]); pst_doubles(y + 2, sin((double)x[0]), cos((double)x[0])); break;
+        case OP_DISK: { /* the signs sample_disk's callers read through lens_uv * 0 */
+            v2 d = sample_disk(V2(x[0], 1.0f));
+            y[0] = d.x; y[1] = d.y; y[2] = copysignf(0.0f, d.x); y[3] = copysignf(0.0f, d.y);
+        } break;
+        case OP_ATAN:
+            y[0] = jl_atan(x[0]); y[1] = jl_sin(y[0]); y[2] = jl_cos(y[0]);
+            pst_doubles(y + 3, sin((double)y[0]), cos((double)y[0]));
+            break;
+        case OP_ATAN2: y[0] = jl_atan2(x[0], x[1]); break;
+        case OP_ACOS: y[0] = jl_acos(x[0]); break;
+        case OP_LOG: y[0] = jl_log(x[0]); break;
+        case OP_EXP: y[0] = jl_exp(x[0]); break;
+        case OP_MINMAX:
+            y[0] = jl_min(x[0], x[1]); y[1] = jl_max(x[0], x[1]);
+            y[2] = jl_min(jl_min(x[0], x[1]), x[2]); y[3] = jl_max(jl_max(x[0], x[1]), x[2]);
+            y[4] = max3f(pld3(x)); y[5] = jl_clamp(x[0], x[1], x[2]);
+            break;
+        case OP_RCP: y[0] = 1.0f / x[0]; break;
+        case OP_BBOX: {
+            ray3 r = {pld3(x), V3(0, 0, 0), x[6], x[7]};
+            y[0] = intersect_bbox(&r, pld3(x + 3), x + 8, x + 11) ? 1.0f : 0.0f;
+        } break;
+        case OP_TRIANGLE: {
+            ray3 r = {pld3(x), pld3(x + 3), x[6], x[7]};
+            prim_isec p = intersect_triangle(&r, pld3(x + 8), pld3(x + 11), pld3(x + 14));
+            pst_isec(y, p); pst_isec(y + 4, p); pst_isec(y + 8, p);
+        } break;
+        case OP_QUAD: {
+            ray3 r = {pld3(x), pld3(x + 3), x[6], x[7]};
+            pst_isec(y, intersect_quad(&r, pld3(x + 8), pld3(x + 11), pld3(x + 14), pld3(x + 17)));
+        } break;
+        case OP_BSDF: {
+            material_point m = probe_material(x);
+            v3 n = pld3(x + 6), o = pld3(x + 9), i = pld3(x + 12);
+            float rnl = x[15];
+            v2 rn = V2(x[16], x[17]);
+            pst3(y, eval_bsdfcos(&m, n, o, i));
+            pst3(y + 3, sample_bsdfcos(&m, n, o, rnl, rn));
+            y[6] = sample_bsdfcos_pdf(&m, n, o, i);
+            pst3(y + 7, eval_delta(&m, n, o, i));
+            pst3(y + 10, sample_delta(&m, n, o, rnl));
+            y[13] = sample_delta_pdf(&m, n, o, i);
+            pst3(y + 14, eval_bsdfcos(&m, n, o, i)); /* the device's fused form restates these two */
+            y[17] = sample_bsdfcos_pdf(&m, n, o, i);
+        } break;
+        case OP_PARTS: {
+            material_point m = probe_material(x);
+            v3 n = pld3(x + 6), o = pld3(x + 9), i = pld3(x + 12);
+            v2 rn = V2(x[16], x[17]);
+            y[0] = fresnel_dielectric(m.ior, n, o);
+            pst3(y + 1, fresnel_conductor(reflectivity_to_eta(m.color), V3(0, 0, 0), n, o));
+            m3 b = basis_fromz(n);
+            pst3(y + 4, b.c1); pst3(y + 7, b.c2); pst3(y + 10, b.c3);
+            pst3(y + 13, sample_hemisphere_cos(n, rn));
+            pst3(y + 16, sample_microfacet(m.roughness, n, rn));
+            pst3(y + 19, refract3(o, n, m.ior));
+            v3 h = normalize3(add3(i, o));
+            y[22] = microfacet_distribution(m.roughness, n, h);
+            y[23] = microfacet_shadowing(m.roughness, n, h, o, i);
+        } break;
+        case OP_VOLUME: {
+            volume_t vol = {pld3(x), pld3(x + 3), x[6]};
+            v3 o = pld3(x + 7), i = pld3(x + 10);
+            pst3(y, eval_transmittance(vol.density, x[15]));
+            y[3] = sample_transmittance(vol.density, x[16], x[17], x[18]);
+            y[4] = sample_transmittance_pdf(vol.density, x[15], x[16]);
+            pst3(y + 5, eval_scattering(&vol, o, i));
+            pst3(y + 8, sample_scattering(&vol, o, 0.0f, V2(x[13], x[14])));
+            y[11] = sample_scattering_pdf(&vol, o, i);
+        } break;
+        default: break;
+    }
+}
+int or_probe(int op, int64_t n, const float* in, float* out) {
+    if (op < 0 || op >= OP_COUNT || n < 0) return -1;
+    const int nin = probe_ops[op].nin, nout = probe_ops[op].nout;
+    for (int64_t i = 0; i < n; i++) probe1(op, in + i * nin, out + i * nout);
+    return 0;
+}
+/* eval_texture of one texture (eval_texture_t above) at n lookups q = (u, v, as_linear) each. */
+int or_probe_texture(int32_t width, int32_t height, int32_t linear, const uint8_t* pixelsb, const float* pixelsf,
+                     int64_t n, const float* q, float* out) {
+    if (width < 0 || height < 0 || (!pixelsb && !pixelsf && width > 0 && height > 0)) return -1;
+    jt_texture t;
+    memset(&t, 0, sizeof(t));
+    t.width = width; t.height = height; t.linear = linear; t.pixelsb = pixelsb; t.pixelsf = pixelsf;
+    for (int64_t i = 0; i < n; i++) {
+        v4 r = eval_texture_t(&t, V2(q[3 * i], q[3 * i + 1]), q[3 * i + 2] != 0.0f);
+        out[4 * i] = r.x; out[4 * i + 1] = r.y; out[4 * i + 2] = r.z; out[4 * i + 3] = r.w;
+    }
+    return 0;
+}

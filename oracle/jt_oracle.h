@@ -70,6 +70,19 @@ void or_srgb_to_rgb(const uint8_t* bytes, int32_t n, float* out);
 /* wide-record property check (tests): records, non-conservative children, leaves, volume ratio x 1000 */
 int or_wide_check(const jt_bvh_tree* tlas, const jt_bvh_tree* blas, int32_t nblas, int64_t* out);
 
+/* Single-primitive probes: op `op` of the table below over n lanes, `in` n x nin floats, `out`
+ * n x nout floats (booleans as 0.0f / 1.0f). The ops, their ids and widths are those of the device
+ * probe library (tests/probe/jt_probe.hip jp_run); a CPU test compares the two tables. Returns 0,
+ * or -1 for an unknown op. */
+int or_probe(int op, int64_t n, const float* in, float* out);
+int or_probe_count(void);
+const char* or_probe_name(int op);
+int or_probe_nin(int op);
+int or_probe_nout(int op);
+/* eval_texture of one texture (bytes or floats, 4 per texel) at n lookups q = n x (u, v, as_linear). */
+int or_probe_texture(int32_t width, int32_t height, int32_t linear, const uint8_t* pixelsb, const float* pixelsf,
+                     int64_t n, const float* q, float* out);
+
 #ifdef __cplusplus
 }
 #endif

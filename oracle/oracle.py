@@ -53,6 +53,13 @@ def _load(abi):
     lib.or_alias_table.argtypes = [f32p, C.c_int32, f32p, C.POINTER(C.c_int32)]
     lib.or_wide_check.argtypes = [C.POINTER(abi.jt_bvh_tree), C.POINTER(abi.jt_bvh_tree), C.c_int32,
                                   C.POINTER(C.c_int64)]
+    lib.or_probe.argtypes = [C.c_int, C.c_int64, f32p, f32p]
+    lib.or_probe_name.argtypes = [C.c_int]
+    lib.or_probe_name.restype = C.c_char_p
+    lib.or_probe_nin.argtypes = [C.c_int]
+    lib.or_probe_nout.argtypes = [C.c_int]
+    lib.or_probe_texture.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8), f32p, C.c_int64, f32p, f32p]
+    lib.or_srgb_to_rgb.argtypes = [C.POINTER(C.c_uint8), C.c_int32, f32p]
     return lib
 
 
@@ -94,6 +101,47 @@ class Oracle:
         if st != 0:
             raise RuntimeError(f"oracle alias table failed: {st}")
         return keep, other
+
+    def probe_ops(self):
+        """The single-primitive probes' table: [(name, nin, nout)], the index is the op id."""
+        return [(self.lib.or_probe_name(k).decode(), self.lib.or_probe_nin(k), self.lib.or_probe_nout(k))
+                for k in range(self.lib.or_probe_count())]
+
+    def probe(self, op, x):
+        """Op `op` (a name of probe_ops) over the rows of x (n, nin) float32: (n, nout) float32."""
+        ops = self.probe_ops()
+        k = [o[0] for o in ops].index(op)
+        x = np.ascontiguousarray(x, np.float32).reshape(-1, ops[k][1])
+        out = np.empty((x.shape[0], ops[k][2]), np.float32)
+        f32p = C.POINTER(C.c_float)
+        st = self.lib.or_probe(k, x.shape[0], x.ctypes.data_as(f32p), out.ctypes.data_as(f32p))
+        if st != 0:
+            raise RuntimeError(f"oracle probe {op} failed: {st}")
+        return out
+
+    def probe_texture(self, pixels, linear, q):
+        """eval_texture of one texture, pixels (H, W, 4) uint8 or float32, at the rows of
+        q (n, 3) = (u, v, as_linear): (n, 4) float32."""
+        pixels = np.ascontiguousarray(pixels)
+        H, W = pixels.shape[:2]
+        q = np.ascontiguousarray(q, np.float32).reshape(-1, 3)
+        out = np.empty((len(q), 4), np.float32)
+        f32p, u8p = C.POINTER(C.c_float), C.POINTER(C.c_uint8)
+        pb = pixels.ctypes.data_as(u8p) if pixels.dtype == np.uint8 else None
+        pf = pixels.ctypes.data_as(f32p) if pixels.dtype == np.float32 else None
+        assert (pb is None) != (pf is None), pixels.dtype
+        st = self.lib.or_probe_texture(W, H, int(bool(linear)), pb, pf, len(q), q.ctypes.data_as(f32p),
+                                       out.ctypes.data_as(f32p))
+        if st != 0:
+            raise RuntimeError(f"oracle texture probe failed: {st}")
+        return out
+
+    def srgb_lut(self):
+        """srgb_to_rgb(byte / 255) of every byte (src/color.jl:12-23), float32."""
+        b = np.arange(256, dtype=np.uint8)
+        out = np.empty(256, np.float32)
+        self.lib.or_srgb_to_rgb(b.ctypes.data_as(C.POINTER(C.c_uint8)), 256, out.ctypes.data_as(C.POINTER(C.c_float)))
+        return out
 
     def wide_check(self, bvh):
         """The wide records of every tree of `bvh` (JT_TRAVERSAL_WIDE): dict of records,
