@@ -358,6 +358,7 @@ typedef struct {
     uint64_t diag[10];
     int path_diff;
     int tie;  /* the current near-first query accepted a hit at exactly its tmax */
+    long nhits; /* hits accepted (every tmax change) by the current run of the current query */
 } scratch_t;
 
 static inline v3 pos3(const jt_shape* s, int32_t v) {
@@ -381,7 +382,8 @@ typedef struct { int instance, element; v2 uv; float distance; int hit; } scene_
  * exactly its current tmax (sc->tie) is run again in the reference's child order (flip 0: the same
  * records visited far child first) and reports that query's hit: the reference's own resolution.
  * `flip` below: 1 visits the near child first (the build's extension), 0 the reference's order. */
-static inline void note_tie(scratch_t* sc, float t, float tmax) { if (t == tmax) sc->tie = 1; }
+/* every accepted primitive hit passes here: the tie note and the query's accepted-hit count */
+static inline void note_tie(scratch_t* sc, float t, float tmax) { sc->nhits++; if (t == tmax) sc->tie = 1; }
 
 /* intersect_shape_bvh (src/bvh.jl:373-491), find_any = false */
 static shape_isec intersect_shape_bvh(const ctx_t* c, int shape_id, ray3 ray, scratch_t* sc, int flip) {
@@ -733,8 +735,12 @@ static scene_isec scene_query1(const ctx_t* c, ray3 ray, scratch_t* sc) {
     const int wide = c->params->traversal == JT_TRAVERSAL_WIDE, near = c->params->traversal != JT_TRAVERSAL_REFERENCE;
     sc->cnt.rays++;
     sc->tie = 0;
+    sc->nhits = 0;
     scene_isec r = wide ? intersect_scene_wide(c, ray, sc, near) : intersect_scene_bvh(c, ray, sc, near);
-    if (near && sc->tie) r = wide ? intersect_scene_wide(c, ray, sc, 0) : intersect_scene_bvh(c, ray, sc, 0);
+    if (near && sc->tie) {
+        sc->nhits = 0; /* the re-run is the query that reports: its own count */
+        r = wide ? intersect_scene_wide(c, ray, sc, 0) : intersect_scene_bvh(c, ray, sc, 0);
+    }
     return r;
 }
 /* or_order_diff: classify the other order's closest hit against this one's, per query */
@@ -761,11 +767,14 @@ static scene_isec instance_query(const ctx_t* c, int inst_id, ray3 ray, scratch_
     const int wide = c->params->traversal == JT_TRAVERSAL_WIDE, near = c->params->traversal != JT_TRAVERSAL_REFERENCE;
     sc->cnt.light_queries++;
     sc->tie = 0;
+    sc->nhits = 0;
     scene_isec r = wide ? intersect_instance_wide(c, inst_id, ray, sc, near) : intersect_instance_bvh(c, inst_id, ray, sc, near);
     /* a one-leaf shape BVH tests its leaf in the same order in every child order: no re-run */
     const jt_bvh_tree* bt = &c->bvh->blas[c->scene->instances[inst_id].shape];
-    if (near && sc->tie && bt->nnodes > 0 && bt->nodes[0].internal)
+    if (near && sc->tie && bt->nnodes > 0 && bt->nodes[0].internal) {
+        sc->nhits = 0;
         r = wide ? intersect_instance_wide(c, inst_id, ray, sc, 0) : intersect_instance_bvh(c, inst_id, ray, sc, 0);
+    }
     return r;
 }
 
@@ -2509,6 +2518,113 @@ int or_intersect_bbox(const float* o, const float* d, float tmin, float tmax, co
     v3 dinv = V3(1 / d[0], 1 / d[1], 1 / d[2]);
     return intersect_bbox(&r, dinv, bmin, bmax);
 }
+/* ------------------------------------------------------------------- ray queries (tests) */
+/* n rays (o, d: 6 floats each) through the traversal params->traversal selects: scene_query, or
+ * instance_query of inst[i] where inst is given and inst[i] >= 0, the tie re-run included.
+ * ids: n x (instance, element, hit), the instance in the reference's numbering; uvt: n x (u, v, t);
+ * counts: n x (hits accepted by the run that reports, nodes, instances, prims of the whole query:
+ * the counters' single-threaded delta). */
+int or_query(const jt_scene* scene, const jt_scene_bvh* bvh, const jt_params* params, int64_t n, const float* rays,
+             const int32_t* inst, int32_t* ids, float* uvt, int64_t* counts) {
+    ctx_t c;
+    jt_lights none = {0, NULL};
+    int st = setup_ctx(&c, scene, bvh, &none, params, 1, 1);
+    scratch_t sc;
+    memset(&sc, 0, sizeof sc);
+    int ssize = params->bvhstacksize > 0 ? params->bvhstacksize : 128;
+    sc.stack = (int32_t*)malloc(sizeof(int32_t) * (size_t)ssize);
+    sc.sub_stack = (int32_t*)malloc(sizeof(int32_t) * (size_t)ssize);
+    sc.stack_size = ssize;
+    if (st == JT_OK && (!sc.stack || !sc.sub_stack)) st = JT_ERR_NOMEM;
+    for (int64_t i = 0; st == JT_OK && i < n; i++) {
+        const float* r = rays + 6 * i;
+        ray3 ray = make_ray(V3(r[0], r[1], r[2]), V3(r[3], r[4], r[5]));
+        const or_counters before = sc.cnt;
+        const int q = inst ? inst[i] : -1;
+        if (q >= scene->ninstances) { st = JT_ERR_INVALID; break; }
+        scene_isec h = q >= 0 ? instance_query(&c, q, ray, &sc) : scene_query(&c, ray, &sc);
+        ids[3 * i] = h.instance;
+        ids[3 * i + 1] = h.element;
+        ids[3 * i + 2] = h.hit;
+        uvt[3 * i] = h.uv.x;
+        uvt[3 * i + 1] = h.uv.y;
+        uvt[3 * i + 2] = h.distance;
+        counts[4 * i] = (int64_t)sc.nhits;
+        counts[4 * i + 1] = (int64_t)(sc.cnt.nodes - before.nodes);
+        counts[4 * i + 2] = (int64_t)(sc.cnt.instances - before.instances);
+        counts[4 * i + 3] = (int64_t)(sc.cnt.prims - before.prims);
+        if (sc.overflow) st = JT_ERR_UNSUPPORTED;
+    }
+    free(sc.stack);
+    free(sc.sub_stack);
+    free_ctx(&c);
+    return st;
+}
+
+/* The ray an instance visit traces: transform_ray by inverse(frame, true) (src/bvh.jl:345, 502). */
+void or_instance_ray(const float* frame, const float* o, const float* d, float* out) {
+    fr3 f = frame_from(frame), inv = inverse_frame(&f, 1);
+    ray3 r = make_ray(V3(o[0], o[1], o[2]), V3(d[0], d[1], d[2])), l = transform_ray(&inv, &r);
+    out[0] = l.o.x, out[1] = l.o.y, out[2] = l.o.z, out[3] = l.d.x, out[4] = l.d.y, out[5] = l.d.z;
+}
+
+/* One primitive of the brute force: element e of the instance's shape against the instance-space ray. */
+static prim_isec brute_prim(const jt_shape* shape, int e, const ray3* ray) {
+    if (shape->ntriangles > 0) {
+        const int32_t* t = &shape->triangles[3 * e];
+        return intersect_triangle(ray, pos3(shape, t[0]), pos3(shape, t[1]), pos3(shape, t[2]));
+    }
+    const int32_t* q = &shape->quads[4 * e];
+    return intersect_quad(ray, pos3(shape, q[0]), pos3(shape, q[1]), pos3(shape, q[2]), pos3(shape, q[3]));
+}
+/* The closest hit of n rays without any BVH: every instance in id order (inst[i] >= 0: that one
+ * only), every element in order, the ray taken into instance space by transform_ray with
+ * inverse(frame, true) as the traversal does, the same intersect_triangle / intersect_quad with
+ * tmin = ray_eps and the inclusive t <= tmax. t: n minimal distances (inf: a miss); nmin: how many
+ * (instance, element) pairs reach it; mins: n x cap pairs, the first cap of them in test order. */
+int or_query_brute(const jt_scene* scene, int64_t n, const float* rays, const int32_t* inst, float* t, int32_t* nmin,
+                   int32_t* mins, int32_t cap) {
+    fr3* inv = (fr3*)malloc(sizeof(fr3) * (size_t)(scene->ninstances + 1));
+    if (!inv) return JT_ERR_NOMEM;
+    for (int k = 0; k < scene->ninstances; k++) {
+        fr3 f = frame_from(scene->instances[k].frame);
+        inv[k] = inverse_frame(&f, 1);
+    }
+    for (int64_t i = 0; i < n; i++) {
+        const float* r = rays + 6 * i;
+        ray3 ray = make_ray(V3(r[0], r[1], r[2]), V3(r[3], r[4], r[5]));
+        const int only = inst ? inst[i] : -1;
+        int found = 0;
+        for (int pass = 0; pass < 2; pass++) { /* 0: the minimal t; 1: everything that reaches it */
+            nmin[i] = 0;
+            if (pass == 1 && !found) break;
+            for (int k = 0; k < scene->ninstances; k++) {
+                if (only >= 0 && k != only) continue;
+                const jt_shape* shape = &scene->shapes[scene->instances[k].shape];
+                const int ne = shape->ntriangles > 0 ? shape->ntriangles : shape->nquads;
+                ray3 lr = transform_ray(&inv[k], &ray);
+                for (int e = 0; e < ne; e++) {
+                    prim_isec p = brute_prim(shape, e, &lr);
+                    if (!p.hit) continue;
+                    if (pass == 0) {
+                        found = 1;
+                        ray.tmax = lr.tmax = p.distance;
+                    } else if (p.distance == ray.tmax) {
+                        if (nmin[i] < cap) {
+                            mins[((size_t)i * cap + nmin[i]) * 2] = k;
+                            mins[((size_t)i * cap + nmin[i]) * 2 + 1] = e;
+                        }
+                        nmin[i]++;
+                    }
+                }
+            }
+        }
+        t[i] = ray.tmax;
+    }
+    free(inv);
+    return JT_OK;
+}
+
 float or_fresnel_dielectric(float eta, const float* normal, const float* outgoing) {
     return fresnel_dielectric(eta, V3(normal[0], normal[1], normal[2]), V3(outgoing[0], outgoing[1], outgoing[2]));
 }

@@ -70,6 +70,22 @@ void or_srgb_to_rgb(const uint8_t* bytes, int32_t n, float* out);
 /* wide-record property check (tests): records, non-conservative children, leaves, volume ratio x 1000 */
 int or_wide_check(const jt_bvh_tree* tlas, const jt_bvh_tree* blas, int32_t nblas, int64_t* out);
 
+/* Ray queries (tests/test_queries_host.py, tests/test_gpu_queries.py). or_query: n rays (o, d: 6
+ * floats each) through the traversal params->traversal selects, the tie re-run included; inst NULL
+ * or per ray -1 for the scene query, >= 0 for the instance query of that instance. ids: n x
+ * (instance in the reference's numbering, element, hit); uvt: n x (u, v, t); counts: n x (hits
+ * accepted by the run that reports — the true count, not saturated —, nodes, instances, prims of
+ * the whole query). or_query_brute: the closest hit with no BVH (every instance in id order, every
+ * element in order, the same transform_ray, intersect_triangle / intersect_quad, tmin = ray_eps,
+ * t <= tmax): t n minimal distances (inf: miss), nmin the number of (instance, element) pairs that
+ * reach it, mins n x cap such pairs in test order. */
+int or_query(const jt_scene* scene, const jt_scene_bvh* bvh, const jt_params* params, int64_t n, const float* rays,
+             const int32_t* inst, int32_t* ids, float* uvt, int64_t* counts);
+int or_query_brute(const jt_scene* scene, int64_t n, const float* rays, const int32_t* inst, float* t, int32_t* nmin,
+                   int32_t* mins, int32_t cap);
+/* the ray (o, d: 6 floats) an instance visit traces: transform_ray by inverse(frame, true) */
+void or_instance_ray(const float* frame, const float* o, const float* d, float* out);
+
 /* Single-primitive probes: op `op` of the table below over n lanes, `in` n x nin floats, `out`
  * n x nout floats (booleans as 0.0f / 1.0f). The ops, their ids and widths are those of the device
  * probe library (tests/probe/jt_probe.hip jp_run); a CPU test compares the two tables. Returns 0,

@@ -60,6 +60,12 @@ def _load(abi):
     lib.or_probe_nout.argtypes = [C.c_int]
     lib.or_probe_texture.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8), f32p, C.c_int64, f32p, f32p]
     lib.or_srgb_to_rgb.argtypes = [C.POINTER(C.c_uint8), C.c_int32, f32p]
+    i32p = C.POINTER(C.c_int32)
+    lib.or_query.argtypes = [C.POINTER(abi.jt_scene), C.POINTER(abi.jt_scene_bvh), C.POINTER(abi.jt_params), C.c_int64,
+                             f32p, i32p, i32p, f32p, i64p]
+    lib.or_query_brute.argtypes = [C.POINTER(abi.jt_scene), C.c_int64, f32p, i32p, f32p, i32p, i32p, C.c_int32]
+    lib.or_instance_ray.argtypes = [f32p, f32p, f32p, f32p]
+    lib.or_instance_ray.restype = None
     return lib
 
 
@@ -135,6 +141,65 @@ class Oracle:
         if st != 0:
             raise RuntimeError(f"oracle texture probe failed: {st}")
         return out
+
+    def query(self, scene_abi, bvh, params, rays, inst=None):
+        """The rows of rays (n, 6) = (o, d) through the traversal params.traversal selects (or_query):
+        scene queries, or the instance query of inst[i] >= 0. Returns a dict of inst, elem, hit
+        (int32), u, v, t (float32), nh (hits accepted by the reporting run, unsaturated), nodes,
+        instances, prims (int64), each of length n."""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        n = len(rays)
+        ids = np.empty((n, 3), np.int32)
+        uvt = np.empty((n, 3), np.float32)
+        cnt = np.empty((n, 4), np.int64)
+        f32p, i32p = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+        ip = None
+        if inst is not None:
+            inst = np.ascontiguousarray(inst, np.int32)
+            assert inst.shape == (n,)
+            ip = inst.ctypes.data_as(i32p)
+        st = self.lib.or_query(scene_abi.ref, C.byref(bvh.struct), C.byref(params), n, rays.ctypes.data_as(f32p), ip,
+                               ids.ctypes.data_as(i32p), uvt.ctypes.data_as(f32p), cnt.ctypes.data_as(C.POINTER(C.c_int64)))
+        if st != 0:
+            raise RuntimeError(f"oracle query failed: {st}")
+        return {"inst": ids[:, 0].copy(), "elem": ids[:, 1].copy(), "hit": ids[:, 2].copy(), "u": uvt[:, 0].copy(),
+                "v": uvt[:, 1].copy(), "t": uvt[:, 2].copy(), "nh": cnt[:, 0].copy(), "nodes": cnt[:, 1].copy(),
+                "instances": cnt[:, 2].copy(), "prims": cnt[:, 3].copy()}
+
+    def query_brute(self, scene_abi, rays, inst=None, cap=8):
+        """The closest hit without a BVH (or_query_brute): t (n,) float32 (inf: a miss), nmin (n,)
+        the number of (instance, element) pairs that reach it, mins (n, cap, 2) the first of them."""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        n = len(rays)
+        t = np.empty(n, np.float32)
+        nmin = np.zeros(n, np.int32)
+        mins = np.full((n, cap, 2), -1, np.int32)
+        f32p, i32p = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+        ip = None
+        if inst is not None:
+            inst = np.ascontiguousarray(inst, np.int32)
+            ip = inst.ctypes.data_as(i32p)
+        st = self.lib.or_query_brute(scene_abi.ref, n, rays.ctypes.data_as(f32p), ip, t.ctypes.data_as(f32p),
+                                     nmin.ctypes.data_as(i32p), mins.ctypes.data_as(i32p), cap)
+        if st != 0:
+            raise RuntimeError(f"oracle brute-force query failed: {st}")
+        return t, nmin, mins
+
+    def instance_ray(self, frame, o, d):
+        """The ray an instance visit traces (or_instance_ray): (o, d) in the instance's space."""
+        f32p = C.POINTER(C.c_float)
+        a = [np.ascontiguousarray(x, np.float32) for x in (frame, o, d)]
+        out = np.empty(6, np.float32)
+        self.lib.or_instance_ray(a[0].ctypes.data_as(f32p), a[1].ctypes.data_as(f32p), a[2].ctypes.data_as(f32p),
+                                 out.ctypes.data_as(f32p))
+        return out[:3], out[3:]
+
+    def intersect_bbox(self, o, d, tmin, tmax, bmin, bmax):
+        """The reference's slab test (or_intersect_bbox), 1/d computed as the traversal computes it."""
+        f32p = C.POINTER(C.c_float)
+        a = [np.ascontiguousarray(x, np.float32) for x in (o, d, bmin, bmax)]
+        return bool(self.lib.or_intersect_bbox(a[0].ctypes.data_as(f32p), a[1].ctypes.data_as(f32p), float(tmin), float(tmax),
+                                               a[2].ctypes.data_as(f32p), a[3].ctypes.data_as(f32p)))
 
     def srgb_lut(self):
         """srgb_to_rgb(byte / 255) of every byte (src/color.jl:12-23), float32."""

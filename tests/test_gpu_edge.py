@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 
 from conftest import compare_images, make_params
-from jtrace.scene import CameraData, InstanceData, MaterialData, SceneData, ShapeData
+from scenes_ref import random_instanced_scene  # moved there unchanged: the ray-query tests build it too
 
 pytestmark = pytest.mark.gpu
 
@@ -109,50 +109,6 @@ def test_one_stream_chunk_on_partial_edge_tiles(gpu, abi, lib, cornell_abi, opti
         for a, name in zip(got[:4], ("image", "albedo", "normal", "hits")):
             assert np.all(a[~mask] == 0), name
         assert np.any(got[0][mask] != 0)
-
-
-def _rotation(rng):
-    q, r = np.linalg.qr(rng.normal(size=(3, 3)))
-    return q * np.sign(np.diag(r))
-
-
-def random_instanced_scene(seed=7):
-    """Random geometry in front of the camera: three shapes (triangles, quads with degenerate
-    ones, a sliver-heavy triangle soup), six instances with rotated and non-uniformly scaled
-    frames, two of them emissive (the lights), matte and glossy materials."""
-    rng = np.random.default_rng(seed)
-    sc = SceneData()
-    cam = np.array([1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 12], np.float32)
-    sc.cameras.append(CameraData(frame=cam, aspect=np.float32(1.0)))
-    sc.materials += [
-        MaterialData(color=np.array([0.7, 0.6, 0.5], np.float32)),
-        MaterialData(type="glossy", color=np.array([0.4, 0.5, 0.8], np.float32), roughness=np.float32(0.3)),
-        MaterialData(emission=np.array([6, 5, 4], np.float32), color=np.zeros(3, np.float32)),
-    ]
-    # shape 0: a triangle soup around the origin. The scene is small enough for the LDS blob
-    # (jt_create takes LDS mode only if it keeps 4 workgroups per CU: about 6 KiB of scene here)
-    n = 10
-    c = rng.normal(size=(n, 1, 3)) * 1.5
-    pos = (c + rng.normal(size=(n, 3, 3)) * 0.4).reshape(-1, 3).astype(np.float32)
-    sc.shapes.append(ShapeData(positions=pos, triangles=np.arange(3 * n, dtype=np.int32).reshape(n, 3)))
-    # shape 1: quads, every third a triangle stored as a degenerate quad (p3 == p4)
-    n = 5
-    c = rng.normal(size=(n, 1, 3))
-    pos = (c + rng.normal(size=(n, 4, 3)) * 0.5).reshape(-1, 3).astype(np.float32)
-    idx = np.arange(4 * n, dtype=np.int32).reshape(n, 4)
-    idx[::3, 3] = idx[::3, 2]
-    sc.shapes.append(ShapeData(positions=pos, quads=idx))
-    # shape 2: a small two-triangle emitter (one BVH leaf: light chains inline)
-    pos = np.array([[-0.5, -0.5, 0], [0.5, -0.5, 0], [0.5, 0.5, 0], [-0.5, 0.5, 0]], np.float32)
-    sc.shapes.append(ShapeData(positions=pos, triangles=np.array([[0, 1, 2], [0, 2, 3]], np.int32)))
-    for i in range(6):
-        shape = 2 if i in (2, 5) else i % 2
-        m = _rotation(rng) * rng.uniform(1.0, 3.0, size=3)  # rotated, non-uniformly scaled axes
-        o = rng.uniform(-4, 4, size=3)
-        o[2] = rng.uniform(-6, 2)
-        frame = np.concatenate([m.reshape(-1), o]).astype(np.float32)
-        sc.instances.append(InstanceData(frame=frame, shape=shape, material=2 if shape == 2 else i % 2))
-    return sc
 
 
 @pytest.fixture(scope="module")

@@ -18,79 +18,16 @@ import numpy as np
 import pytest
 
 from conftest import compare_images, make_params
-from jtrace.scene import CameraData, EnvironmentData, InstanceData, MaterialData, SceneData, ShapeData, TextureData
+from scenes_ref import SEEDS, quad_scene, strip_scene  # moved there unchanged: the ray-query tests build them too
 
 pytestmark = pytest.mark.gpu
 
 ORDERS = {"reference": 0, "near": 1}
 QUADS = (1, 2, 3, 5, 7, 9)
-# seeds of the instance positions, searched on the CPU with the oracle's BVH build so that TLAS
-# leaves of 1, 2, 3 and 4 instances all occur across the set (asserted below)
-SEEDS = {1: 1, 2: 1, 3: 1, 5: 4, 7: 1, 9: 4}
 W = H = 48
 SPP = 4
 NODE = np.dtype([("bmin", "<f4", 3), ("bmax", "<f4", 3), ("start", "<i4"), ("num", "<i2"), ("axis", "i1"),
                  ("internal", "i1")])
-
-
-def _rotation(rng):
-    q, r = np.linalg.qr(rng.normal(size=(3, 3)))
-    return q * np.sign(np.diag(r))
-
-
-def _identity():
-    return np.array([1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0], np.float32)
-
-
-def _camera(sc):
-    sc.cameras.append(CameraData(frame=np.array([1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 12], np.float32),
-                                 aspect=np.float32(1.0)))
-
-
-def quad_scene(n, glossy, seed):
-    """n two-triangle quads and one 12-triangle box in front of the camera, each its own shape in
-    world coordinates under an identity frame; quad 0 is the light."""
-    rng = np.random.default_rng(1000 * n + seed)
-    sc = SceneData()
-    _camera(sc)
-    sc.materials += [
-        MaterialData(color=np.array([0.7, 0.6, 0.5], np.float32)),
-        MaterialData(emission=np.array([8, 7, 6], np.float32), color=np.zeros(3, np.float32)),
-        MaterialData(type="glossy", color=np.array([0.4, 0.5, 0.8], np.float32), roughness=np.float32(0.3))
-        if glossy else MaterialData(color=np.array([0.3, 0.6, 0.4], np.float32)),
-    ]
-    unit = np.array([[-1, -1, 0], [1, -1, 0], [1, 1, 0], [-1, 1, 0]], np.float64)
-    for k in range(n):
-        centre = np.array([0.0, 0.0, 2.5]) if k == 0 else rng.uniform([-3.5, -3.5, -4], [3.5, 3.5, 1])
-        pos = (unit * rng.uniform(0.8, 1.6)) @ _rotation(rng).T + centre
-        sc.shapes.append(ShapeData(positions=pos.astype(np.float32), triangles=np.array([[0, 1, 2], [0, 2, 3]], np.int32)))
-        sc.instances.append(InstanceData(frame=_identity(), shape=k, material=1 if k == 0 else 0))
-    corners = np.array([[x, y, z] for x in (-1, 1) for y in (-1, 1) for z in (-1, 1)], np.float64)
-    tris = np.array([[0, 1, 3], [0, 3, 2], [4, 6, 7], [4, 7, 5], [0, 4, 5], [0, 5, 1], [2, 3, 7], [2, 7, 6],
-                     [0, 2, 6], [0, 6, 4], [1, 5, 7], [1, 7, 3]], np.int32)
-    pos = (corners * 0.9) @ _rotation(rng).T + rng.uniform([-2, -2, -2], [2, 2, 0])
-    sc.shapes.append(ShapeData(positions=pos.astype(np.float32), triangles=tris))
-    sc.instances.append(InstanceData(frame=_identity(), shape=n, material=2))
-    return sc
-
-
-def strip_scene():
-    """One instance of a 64-triangle strip along x, folded at x = 0 so its wings see each other,
-    under a constant environment (the scene's only light: an emissive strip's light records would
-    push the scene out of LDS mode)."""
-    sc = SceneData()
-    _camera(sc)
-    sc.materials.append(MaterialData(color=np.array([0.6, 0.6, 0.6], np.float32)))
-    sc.textures.append(TextureData(width=2, height=2, linear=True, pixelsf=np.ones((2, 2, 4), np.float32)))
-    sc.environments.append(EnvironmentData(frame=_identity(), emission=np.array([1.0, 0.9, 0.8], np.float32),
-                                           emission_tex=0))
-    x = np.linspace(-4, 4, 33)
-    pos = np.array([[xi, y, 1.2 * abs(xi) - 3] for xi in x for y in (-1.5, 1.5)], np.float32)
-    tris = np.array([t for i in range(32) for t in ([2 * i, 2 * i + 2, 2 * i + 3], [2 * i, 2 * i + 3, 2 * i + 1])], np.int32)
-    assert len(tris) == 64
-    sc.shapes.append(ShapeData(positions=pos, triangles=tris))
-    sc.instances.append(InstanceData(frame=_identity(), shape=0, material=0))
-    return sc
 
 
 def tlas_leaf_sizes(bvh):
