@@ -23,6 +23,8 @@
  *   jt_denoise_guided  (the build's own) the a-trous filter with that variance as its colour tolerance
  *   jt_adapt           (the build's own) adaptive sampling: 8x8 tiles whose variance meets a noise
  *                      target take no more samples; jt_get_sample_counts the samples per pixel
+ *   jt_intersect       ~ intersect_scene_bvh / intersect_instance_bvh (src/bvh.jl:306-520) for the
+ *                      caller's own rays on the context's scene; jt_occluded its find_any form
  *   jt_destroy / jt_last_error — lifetime and error reporting (the reference throws Julia exceptions)
  *
  * Host helpers (run on the CPU, no device needed) that restate the reference's host code
@@ -541,6 +543,52 @@ int jt_get_noise(jt_ctx* ctx, double* noise);
  * share does not trace; all n on a context that never adapted. */
 int jt_adapt(jt_ctx* ctx, double noise_target, int32_t* active_tiles /* may be NULL */);
 int jt_get_sample_counts(jt_ctx* ctx, int32_t* counts /* W*H */);
+
+/* ---- ray queries ------------------------------------------------------------------------- */
+/* Closest-hit and any-hit queries of arbitrary rays against the context's scene: the traversal
+ * the path integrator itself runs (src/bvh.jl:306-520), for callers who want what is under a
+ * pixel, visibility, depth or instance-id maps, ambient occlusion or probe placement. */
+typedef struct jt_hit {      /* 24 bytes */
+    int32_t instance;        /* index into jt_scene.instances (the caller's numbering), -1: miss */
+    int32_t element;         /* triangle / quad index within the instance's shape, -1: miss */
+    float u, v;              /* element uv as the reference's intersection.uv; 0 on a miss */
+    float t;                 /* distance; +inf on a miss */
+    int32_t hit;             /* 1 / 0 */
+} jt_hit;
+/* jt_intersect: for every ray i (rays[6 i ..] = origin, direction) the closest hit of the
+ * reference's intersect_scene_bvh(..., find_any = false), or, where instance is not NULL and
+ * instance[i] >= 0, of intersect_instance_bvh of that instance. It runs in the traversal the
+ * context was created with (reference, near or wide, JT_TRAVERSAL_AUTO as resolved), the re-run
+ * of an exact-t tie included: the hit the integrator would find for that ray, bit for bit, whatever
+ * the number of rays and their order. Rays are unbounded, as every query of the reference is:
+ * tmax is infinite, tmin is the reference's ray_eps inside the primitive tests. The direction
+ * need not be normalised; t is in units of it.
+ * jt_occluded: find_any = true reduced to its flag. A ray's query ends at its first accepted hit
+ * and is never re-run for a tie. Until a hit is accepted tmax is infinite, exactly as in the
+ * closest-hit query, so both queries take the same steps in the same order up to that hit: the
+ * any-hit query visits a prefix of the closest-hit query's steps and accepts a hit iff that
+ * query accepts one. occluded[i] therefore equals jt_intersect's hit for every ray (the near-first
+ * orders' tie re-run never turns a hit into a miss: it runs only after a hit was accepted, and
+ * finds the same primitives), for less work.
+ * Instances are numbered as in jt_scene.instances, in the argument and in the results.
+ * The *_device variants take device pointers on the context's device (d_instance may be NULL),
+ * run on the context's stream and return when it is idle; in them an instance id outside
+ * -1 .. ninstances-1 reports a miss. The host variants stage through buffers the context owns
+ * (allocated by the first call, grown when needed, kept across jt_reset, freed by jt_destroy).
+ * A query reads the scene only: image, AOVs, stream means, variance, the adaptive mask and every
+ * jt_counters field stay bit for bit as they were, queued samples stay queued, and query work
+ * is not counted. A context that never queries behaves exactly as before.
+ * Errors, in this order: JT_ERR_INVALID (naming the argument) for a NULL ctx, rays or output,
+ * n < 0 or n > 2^30, before the context is looked at; n == 0 returns JT_OK with no device work;
+ * JT_ERR_UNSUPPORTED for a multi-device context (jt_create_multi); JT_ERR_STATE for a failed
+ * context; JT_ERR_INVALID for a host instance[i] outside -1 .. ninstances-1.
+ * Non-finite ray components are the caller's responsibility: the query terminates for any input
+ * (every step pops an entry of a finite tree), the result for such a ray is unspecified. */
+int jt_intersect(jt_ctx* ctx, int64_t n, const float* rays /* n x (o, d), 6 floats */,
+                 const int32_t* instance /* NULL, or per ray -1 / an instance id */, jt_hit* hits);
+int jt_occluded(jt_ctx* ctx, int64_t n, const float* rays, uint8_t* occluded /* n */);
+int jt_intersect_device(jt_ctx* ctx, int64_t n, const void* d_rays, const void* d_instance, void* d_hits);
+int jt_occluded_device(jt_ctx* ctx, int64_t n, const void* d_rays, void* d_occluded);
 
 /* zero accumulators (at once if their device pointers were handed out, else before they are
  * next read or overwritten), samples = 0, queued samples dropped */

@@ -1,7 +1,7 @@
 // jt_context.h — the device context behind include/jtrace.h's jt_ctx and the few functions its
 // pieces share: jt_trace.hip (creation, the sample queue, the getters), jt_multi.hip (the
-// multi-device context), jt_denoise.hip, jt_error.hip and jt_adapt.hip (their context halves). Not
-// part of the ABI.
+// multi-device context), jt_denoise.hip, jt_error.hip, jt_adapt.hip and jt_intersect.hip (their
+// context halves). Not part of the ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -94,6 +94,22 @@ struct jt_ctx {
     int adapt_active = 0;   // traced tiles still active after the last jt_adapt (all after jt_reset)
     bool adapted = false;   // jt_adapt has run on this context (jt_describe)
 
+    // ---- ray queries
+    // jt_intersect, jt_occluded (jt_intersect.hip). inst_new: the caller's instance id -> the device's
+    // (layout_scene's permutation, kept by jt_create). Uploaded by the first query, in
+    // `allocations`: that permutation and its inverse, and the launch's ray counter. q_grow: the
+    // buffers that grow with the calls — the query grid's own stack overflow area (q_ovf_entries
+    // ints) and the host variants' staging of rays, instance ids and results (q_stage_rays
+    // rays) — kept across jt_reset, freed by jt_destroy (query_free)
+    std::vector<int> inst_new;
+    int* q_to_dev = nullptr;
+    int* q_to_ref = nullptr;
+    unsigned* q_counter = nullptr;
+    enum { Q_OVF = 0, Q_RAYS, Q_INST, Q_OUT, Q_NGROW };
+    void* q_grow[Q_NGROW] = {nullptr, nullptr, nullptr, nullptr};
+    size_t q_ovf_entries = 0;
+    long long q_stage_rays = 0;
+
     // ---- a multi-device context (jt_create_multi) owns its sub-contexts and reduce state here
     // and uses, of the fields above, only the size, the sample counts, the queue, `failed`,
     // `denoised`, the counters' totals, and device 0's `lk` and `exported`
@@ -117,6 +133,8 @@ int trace_finish(jt_ctx* c, float* ms);
 // trace the deferred samples [pend0, pend1) (jt_ctx) and wait for them; every call that reads
 // the context's results or device buffers runs this first
 int flush(jt_ctx* c);
+// frees the ray queries' growing buffers (jt_ctx::q_grow; jt_intersect.hip), for jt_destroy
+void query_free(jt_ctx* c);
 
 // xyz of np float4 to np x 3 floats (the AOV getters)
 inline void unpack3(const std::vector<float4>& src, float* dst) {

@@ -1,0 +1,66 @@
+// jt_intersect.h — the integer rules of a ray queries' launch (include/jtrace.h: jt_intersect,
+// jt_occluded; the kernel and the context's half are in jt_intersect.hip): the persistent grid for n
+// rays, the size of its stack overflow area, the growth of the host variants' staging buffers.
+// Plain C++ (no HIP runtime), shared by jt_intersect.hip and the host check (tests/query_plan_check.cpp).
+// Not part of the ABI.
+#pragma once
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "jt_select.h"  // BLOCK
+
+namespace jtq {
+
+constexpr int64_t QUERY_MAX_RAYS = (int64_t)1 << 30;  // rays of one call (the ray counter is 32 bits)
+constexpr int QUERY_WG_PER_CU = 8;  // workgroups per compute unit of the persistent grid, at most
+constexpr int QUERY_RING = 16;      // entries of the LDS stack ring: 16 KiB per workgroup
+// a wave hands new rays to its finished lanes once this many of them have none: fewer and a
+// refill's ray loads serve few lanes, more and finished lanes idle longer
+constexpr int QUERY_REFILL_LANES = 16;
+// the step-kind vote: one lane that wants a primitive test outvotes this many that want a node step
+// (the megakernel's JT_VOTE_P)
+constexpr int QUERY_VOTE_P = 3;
+
+// Workgroups of the launch for n >= 1 rays: one lane per ray up to the persistent grid of
+// cus * QUERY_WG_PER_CU workgroups, whose waves then claim the other rays as their lanes finish.
+inline int query_grid(int64_t n, int cus) {
+    const int64_t full = (int64_t)(cus < 1 ? 1 : cus) * QUERY_WG_PER_CU;
+    const int64_t want = (n + jtk::BLOCK - 1) / jtk::BLOCK;
+    return (int)(want < 1 ? 1 : want < full ? want : full);
+}
+
+// Entries (ints) of the grid's HBM stack overflow area: the scene's stack bound `need` per lane;
+// a lane's slot is blockIdx.x * BLOCK + threadIdx.x.
+inline size_t query_ovf_entries(int grid, int need) { return (size_t)grid * jtk::BLOCK * (size_t)need; }
+
+// Rays a wave claims with one atomicAdd on the launch's ray counter, its reserve for the next
+// refills: QUERY_CLAIM_MAX when every wave of the grid can have that many (one same-address
+// atomic per refill bound a launch of 2^22 rays to 2.4 ms), down to 64, a ray per lane, for a
+// small call, so that its rays spread over all its waves; a power of two.
+constexpr int QUERY_CLAIM_MAX = 256;
+inline int query_claim_rays(int64_t n, int grid) {
+    const int64_t waves = (int64_t)grid * (jtk::BLOCK / 64);
+    int claim = 64;
+    while (claim < QUERY_CLAIM_MAX && (int64_t)claim * 2 * waves <= n) claim *= 2;
+    return claim;
+}
+
+// The most the ray counter reaches: the last claim that starts below n ends below n +
+// QUERY_CLAIM_MAX, and every wave stops claiming at its first claim that starts at or past n: one
+// more claim per wave of the grid (< 2^32: the counter is 32 bits).
+inline uint64_t query_counter_bound(int64_t n, int grid) {
+    return (uint64_t)n + (uint64_t)QUERY_CLAIM_MAX * ((uint64_t)grid * (jtk::BLOCK / 64) + 1);
+}
+
+// Rays the staging buffers hold after a call of n rays when they held `have`: unchanged while n
+// fits; else at least twice as many (so m growing calls copy O(m) buffers' worth), rounded up to
+// 1024 rays, at most QUERY_MAX_RAYS.
+inline int64_t query_stage_rays(int64_t have, int64_t n) {
+    if (n <= have) return have;
+    int64_t want = n > 2 * have ? n : 2 * have;
+    want = (want + 1023) / 1024 * 1024;
+    return want > QUERY_MAX_RAYS ? QUERY_MAX_RAYS : want;
+}
+
+}  // namespace jtq

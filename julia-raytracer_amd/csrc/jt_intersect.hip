@@ -1,0 +1,342 @@
+// jt_intersect.hip — ray queries on a context's scene (include/jtrace.h: jt_intersect, jt_occluded and
+// their device-pointer variants; DESIGN.md §6e "Ray queries"): the megakernel's own traversal
+// (jt_traverse.h) over the caller's rays.
+//
+// The scene is the context's HBM copy — every array of JT_SCENE_ARRAYS is uploaded in both scene
+// modes, so an LDS-mode context queries through HBM pointers too (NCACHE) — with the general feature
+// mask (the traversal tells masks apart by FT_XFORM and FT_QUAD only), no counters, the 16-entry
+// LDS stack ring, and for a scene whose bound exceeds the ring an HBM overflow area of the query
+// grid's own. Per lane the loop is
+//     query_start<WIDE>; until query_done<WIDE>: prim_step if nprim > 0, else node_step_any;
+//     then rerun_tie<WIDE>, and the loop again if it re-runs
+// and an any-hit query (ANY) leaves it at its first accepted hit instead. A ray's result depends
+// on the ray and the scene only, never on the lane that runs it or on when.
+//
+// Work distribution: query lengths diverge by orders of magnitude (a miss from outside costs one
+// box test, a ray through a deep scene hundreds of nodes), so the grid is persistent — at most
+// QUERY_WG_PER_CU workgroups per compute unit (jt_intersect.h) — and a wave refills its finished lanes
+// once QUERY_REFILL_LANES of them have no ray: a ballot of those lanes, and the k-th of them takes
+// the k-th ray of the wave's reserve (the megakernel's hand-out, jt_kernels.h). The reserve is
+// query_claim_rays consecutive rays (64 to 256), claimed by the wave's first lane with one atomicAdd on the
+// launch's ray counter: a claim per refill (a fifth of a million same-address atomics for 2^22
+// rays) bound the whole launch to 2.4 ms whatever the scene (EXPERIMENTS.md). Each iteration then
+// runs one step kind, primitive tests or node steps, picked by the megakernel's biased lane vote.
+// A lane writes its ray's record when its query ends.
+#include <hip/hip_runtime.h>
+
+#include <string>
+#include <vector>
+
+#include "jt_context.h"
+#include "jt_intersect.h"
+#include "jt_traverse.h"
+
+namespace jtk {
+
+using jtq::QUERY_REFILL_LANES;
+using jtq::QUERY_VOTE_P;
+using jtq::QUERY_RING;
+
+struct DQuery {
+    const float* rays;     // n x (o, d)
+    const int* inst;       // nullptr, or per ray -1 / an instance id in the caller's numbering
+    int* hits;             // closest hit: n jt_hit records as 6 words each
+    unsigned char* occ;    // any hit: n flags
+    unsigned* counter;     // the next ray to claim (zeroed before the launch)
+    const int* to_dev;     // the caller's instance id -> the device's (TLAS leaf order)
+    const int* to_ref;     // and back
+    int n, ninst;
+    unsigned claim;        // rays a wave claims with one atomic (query_claim_rays)
+};
+
+constexpr int Q_BAD_INSTANCE = -2;
+// the device instance of ray `ray`'s query: -1 a scene query, Q_BAD_INSTANCE an id out of range
+__device__ __forceinline__ int query_instance(const DQuery& Q, int ray) {
+    if (!Q.inst) return -1;
+    const int id = Q.inst[ray];
+    if (id == -1) return -1;
+    return id >= 0 && id < Q.ninst ? Q.to_dev[id] : Q_BAD_INSTANCE;
+}
+
+__device__ __forceinline__ void write_hit(const DQuery& Q, int ray, const Hit& h) {
+    int* const y = Q.hits + (size_t)ray * 6;
+    y[0] = h.hit ? Q.to_ref[h.inst] : -1;
+    y[1] = h.elem;
+    y[2] = __float_as_int(h.u);
+    y[3] = __float_as_int(h.v);
+    y[4] = __float_as_int(h.t);
+    y[5] = h.hit ? 1 : 0;
+}
+
+// the lane starts ray `ray`'s query; false: its instance id is out of range, a miss is recorded
+template <bool WIDE, bool ANY>
+__device__ __forceinline__ bool query_take(const DScene& S, const DQuery& Q, Trav& T, int ray, int* stack) {
+    const int q = query_instance(Q, ray);
+    if (q == Q_BAD_INSTANCE) {
+        if (ANY) Q.occ[ray] = 0;
+        else write_hit(Q, ray, Hit{-1, -1, 0.0f, 0.0f, __builtin_inff(), false});
+        return false;
+    }
+    const float* const r = Q.rays + (size_t)ray * 6;
+    query_start<WIDE>(S, T, V3(r[0], r[1], r[2]), V3(r[3], r[4], r[5]), q, stack);
+    return true;
+}
+
+template <bool WIDE, bool OVF, bool ANY>
+__global__ __launch_bounds__(BLOCK) void query_kernel(DScene S, DQuery Q) {
+    constexpr int F = FT_ALL;
+    __shared__ int ring[QUERY_RING * BLOCK];
+    int* const stack = ring + threadIdx.x;
+    const int slot = (int)blockIdx.x * BLOCK + (int)threadIdx.x;  // the lane's HBM stack-overflow area
+    Counters cnt{0, 0, 0, 0};
+    Trav T;
+    int ray = -1;  // the lane's ray; -1: none
+    bool drained = false;          // every ray is claimed
+    unsigned wnext = 0, wend = 0;  // the wave's reserve of claimed rays [wnext, wend)
+    for (;;) {
+        // ---- refill (wave-uniform control): the k-th lane without a ray takes the k-th ray of the
+        // wave's reserve
+        const unsigned long long idle = __builtin_amdgcn_ballot_w64(ray < 0);
+        const int nidle = __popcll(idle);
+        if (nidle == 64 && drained) break;
+        if (!drained && nidle >= QUERY_REFILL_LANES) {
+            if (wnext >= wend) {  // the wave's reserve is empty: claim Q.claim consecutive rays
+                unsigned base = 0;
+                if ((threadIdx.x & 63) == 0) base = atomicAdd(Q.counter, Q.claim);
+                base = __builtin_amdgcn_readfirstlane(base);
+                wnext = base;
+                wend = base + Q.claim < (unsigned)Q.n ? base + Q.claim : (unsigned)Q.n;  // < 2^32: query_counter_bound
+                drained = base >= (unsigned)Q.n;
+            }
+            if (!drained) {
+                const unsigned avail = wend - wnext, take = (unsigned)nidle < avail ? (unsigned)nidle : avail;
+                const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(idle >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)idle, 0u));
+                if (ray < 0 && rank < take && query_take<WIDE, ANY>(S, Q, T, (int)(wnext + rank), stack)) ray = (int)(wnext + rank);
+                wnext += take;
+            }
+        }
+        // ---- one step of every lane with a query in flight: one step kind per iteration, by a
+        // biased lane vote (the megakernel's, jt_kernels.h), so the SIMD runs one code path; a lane's
+        // own sequence of steps is unchanged, it only waits while the other kind runs
+        const bool wantp = ray >= 0 && T.nprim > 0, wantn = ray >= 0 && T.nprim == 0;
+        const int np = __popcll(__builtin_amdgcn_ballot_w64(wantp)), nn = __popcll(__builtin_amdgcn_ballot_w64(wantn));
+        if (np * QUERY_VOTE_P >= nn) {
+            if (wantp) prim_step<0, F>(S, T, cnt);
+        } else {
+            if (wantn) node_step_any<WIDE, QUERY_RING, OVF, 0, true, F>(S, T, stack, slot, cnt);
+        }
+        // ---- a lane whose query has ended records it
+        if (ray >= 0) {
+            if (ANY) {  // the first accepted hit ends the query; never re-run for a tie
+                if (T.h_inst >= 0 || query_done<WIDE>(T)) {
+                    Q.occ[ray] = T.h_inst >= 0 ? 1 : 0;
+                    ray = -1;
+                }
+            } else if (query_done<WIDE>(T) && !rerun_tie<WIDE>(S, T, T.wo, T.wd, query_instance(Q, ray), stack)) {
+                write_hit(Q, ray, query_hit(T));
+                ray = -1;
+            }
+        }
+    }
+}
+
+}  // namespace jtk
+
+// ---- the context's half (jt_context.h)
+using namespace jtc;
+using jtd::DScene;
+
+namespace {
+
+constexpr int BLOCK = jtk::BLOCK;
+
+template <bool WIDE, bool OVF, bool ANY>
+void launch_query(int grid, hipStream_t stream, const DScene& S, const jtk::DQuery& Q) {
+    hipLaunchKernelGGL((jtk::query_kernel<WIDE, OVF, ANY>), dim3((unsigned)grid), dim3(BLOCK), 0, stream, S, Q);
+}
+
+// a buffer of jt_ctx::q_grow of at least `bytes` (the old one is freed first: its content is not kept)
+int grow(jt_ctx* c, int which, size_t bytes, const char* what) {
+    if (c->q_grow[which]) (void)hipFree(c->q_grow[which]);
+    c->q_grow[which] = nullptr;
+    if (hipMalloc(&c->q_grow[which], bytes) != hipSuccess) {
+        c->q_grow[which] = nullptr;
+        (void)hipGetLastError();
+        return jt::fail(JT_ERR_NOMEM, std::string("hipMalloc ") + what);
+    }
+    return JT_OK;
+}
+
+// the first query's uploads: the instance permutation both ways and the ray counter
+int query_setup(jt_ctx* c) {
+    if (c->q_counter) return JT_OK;
+    const size_t ni = c->inst_new.size();
+    std::vector<int> to_ref(ni, -1);
+    for (size_t k = 0; k < ni; k++) to_ref[(size_t)c->inst_new[k]] = (int)k;
+    void *a = nullptr, *b = nullptr, *w = nullptr;
+    int st;
+    const size_t bytes = (ni ? ni : 1) * sizeof(int);
+    if ((st = device_alloc(c, bytes, "query instance ids", &a)) || (st = device_alloc(c, bytes, "query instance ids", &b)) ||
+        (st = device_alloc(c, sizeof(unsigned), "query ray counter", &w)))
+        return st;
+    hipError_t e;
+    if (ni && ((e = hipMemcpy(a, c->inst_new.data(), bytes, hipMemcpyHostToDevice)) != hipSuccess ||
+               (e = hipMemcpy(b, to_ref.data(), bytes, hipMemcpyHostToDevice)) != hipSuccess))
+        return hip_fail(e, "hipMemcpy query instance ids");
+    c->q_to_dev = (int*)a;
+    c->q_to_ref = (int*)b;
+    c->q_counter = (unsigned*)w;
+    return JT_OK;
+}
+
+// the checks every entry point shares, in the header's order; *done: n == 0, nothing to do
+int query_check(const jt_ctx* c, int64_t n, const void* rays, const char* rays_name, const void* out, const char* out_name,
+                bool* done) {
+    *done = false;
+    if (!c) return jt::fail(JT_ERR_INVALID, "ctx is NULL");
+    if (!rays) return jt::fail(JT_ERR_INVALID, std::string(rays_name) + " is NULL");
+    if (!out) return jt::fail(JT_ERR_INVALID, std::string(out_name) + " is NULL");
+    if (n < 0) return jt::fail(JT_ERR_INVALID, "n must be at least 0");
+    if (n > jtq::QUERY_MAX_RAYS) return jt::fail(JT_ERR_INVALID, "n must be at most 2^30 rays");
+    if (n == 0) {
+        *done = true;
+        return JT_OK;
+    }
+    if (c->multi)
+        return jt::fail(JT_ERR_UNSUPPORTED,
+                        "ray queries are not available on a multi-device context (jt_create_multi): query one context per device");
+    if (c->failed) return jt::fail(JT_ERR_STATE, "a previous launch failed; jt_reset the context");
+    return JT_OK;
+}
+
+// n >= 1 rays from device pointers, on the context's stream; returns once the stream is idle
+int query_run(jt_ctx* c, int64_t n, const void* d_rays, const void* d_inst, void* d_out, bool any) {
+    (void)hipSetDevice(c->device);
+    int st = query_setup(c);
+    if (st != JT_OK) return st;
+    const int grid = jtq::query_grid(n, c->cus);
+    DScene S = c->S;
+    // the context's ring entries in use (option test_lds_ring shortens it), within this kernel's ring
+    S.ring = c->S.ring < jtq::QUERY_RING ? c->S.ring : jtq::QUERY_RING;
+    const int need = c->S.stack_need;
+    const bool ovf = need > S.ring;
+    S.ovf = nullptr;
+    S.ovf_stride = 0;
+    if (ovf) {  // an overflow area of this grid's own (the trace kernel's belongs to its grid)
+        const size_t entries = jtq::query_ovf_entries(grid, need);
+        if (entries > c->q_ovf_entries) {
+            c->q_ovf_entries = 0;
+            if ((st = grow(c, jt_ctx::Q_OVF, entries * sizeof(int), "query stack overflow")) != JT_OK) return st;
+            c->q_ovf_entries = entries;
+        }
+        S.ovf = (int*)c->q_grow[jt_ctx::Q_OVF];
+        S.ovf_stride = need;
+    }
+    jtk::DQuery Q{};
+    Q.rays = (const float*)d_rays;
+    Q.inst = (const int*)d_inst;
+    Q.hits = any ? nullptr : (int*)d_out;
+    Q.occ = any ? (unsigned char*)d_out : nullptr;
+    Q.counter = c->q_counter;
+    Q.to_dev = c->q_to_dev;
+    Q.to_ref = c->q_to_ref;
+    Q.n = (int)n;
+    Q.ninst = (int)c->inst_new.size();
+    Q.claim = (unsigned)jtq::query_claim_rays(n, grid);
+    hipError_t e = hipMemsetAsync(c->q_counter, 0, sizeof(unsigned), c->stream);
+    if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync query ray counter");
+    const int form = (c->choice.wide ? 4 : 0) | (ovf ? 2 : 0) | (any ? 1 : 0);
+    switch (form) {
+        case 0: launch_query<false, false, false>(grid, c->stream, S, Q); break;
+        case 1: launch_query<false, false, true>(grid, c->stream, S, Q); break;
+        case 2: launch_query<false, true, false>(grid, c->stream, S, Q); break;
+        case 3: launch_query<false, true, true>(grid, c->stream, S, Q); break;
+        case 4: launch_query<true, false, false>(grid, c->stream, S, Q); break;
+        case 5: launch_query<true, false, true>(grid, c->stream, S, Q); break;
+        case 6: launch_query<true, true, false>(grid, c->stream, S, Q); break;
+        default: launch_query<true, true, true>(grid, c->stream, S, Q); break;
+    }
+    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "query kernel launch");
+    if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) {
+        c->failed = true;
+        return hip_fail(e, "query kernel");
+    }
+    return JT_OK;
+}
+
+// the host variants: rays (and instance ids) staged to the device, the results copied back
+int query_host(jt_ctx* c, int64_t n, const float* rays, const int32_t* instance, void* out, bool any) {
+    (void)hipSetDevice(c->device);
+    const size_t N = (size_t)n;
+    if (n > c->q_stage_rays) {
+        const size_t cap = (size_t)jtq::query_stage_rays(c->q_stage_rays, n);
+        c->q_stage_rays = 0;
+        int st;
+        if ((st = grow(c, jt_ctx::Q_RAYS, cap * 6 * sizeof(float), "query rays")) ||
+            (st = grow(c, jt_ctx::Q_INST, cap * sizeof(int32_t), "query instance ids")) ||
+            (st = grow(c, jt_ctx::Q_OUT, cap * sizeof(jt_hit), "query results")))
+            return st;
+        c->q_stage_rays = (long long)cap;
+    }
+    void* const d_rays = c->q_grow[jt_ctx::Q_RAYS];
+    void* const d_inst = instance ? c->q_grow[jt_ctx::Q_INST] : nullptr;
+    void* const d_out = c->q_grow[jt_ctx::Q_OUT];
+    hipError_t e;
+    if ((e = hipMemcpy(d_rays, rays, N * 6 * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess ||
+        (instance && (e = hipMemcpy(d_inst, instance, N * sizeof(int32_t), hipMemcpyHostToDevice)) != hipSuccess))
+        return hip_fail(e, "hipMemcpy query rays");
+    const int st = any ? jt_occluded_device(c, n, d_rays, d_out) : jt_intersect_device(c, n, d_rays, d_inst, d_out);
+    if (st != JT_OK) return st;
+    if ((e = hipMemcpy(out, d_out, any ? N : N * sizeof(jt_hit), hipMemcpyDeviceToHost)) != hipSuccess)
+        return hip_fail(e, "hipMemcpy query results");
+    return JT_OK;
+}
+
+}  // namespace
+
+void jtc::query_free(jt_ctx* c) {
+    for (void*& p : c->q_grow) {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+    }
+    c->q_ovf_entries = 0;
+    c->q_stage_rays = 0;
+}
+
+static_assert(sizeof(jt_hit) == 24, "the query kernel writes a jt_hit as six 32-bit words");
+
+extern "C" {
+
+int jt_intersect_device(jt_ctx* c, int64_t n, const void* d_rays, const void* d_instance, void* d_hits) {
+    bool done;
+    if (const int st = query_check(c, n, d_rays, "d_rays", d_hits, "d_hits", &done)) return st;
+    return done ? JT_OK : query_run(c, n, d_rays, d_instance, d_hits, false);
+}
+
+int jt_occluded_device(jt_ctx* c, int64_t n, const void* d_rays, void* d_occluded) {
+    bool done;
+    if (const int st = query_check(c, n, d_rays, "d_rays", d_occluded, "d_occluded", &done)) return st;
+    return done ? JT_OK : query_run(c, n, d_rays, nullptr, d_occluded, true);
+}
+
+int jt_intersect(jt_ctx* c, int64_t n, const float* rays, const int32_t* instance, jt_hit* hits) {
+    bool done;
+    if (const int st = query_check(c, n, rays, "rays", hits, "hits", &done)) return st;
+    if (done) return JT_OK;
+    if (instance) {
+        const int64_t ni = (int64_t)c->inst_new.size();
+        for (int64_t i = 0; i < n; i++)
+            if (instance[i] < -1 || instance[i] >= ni)
+                return jt::fail(JT_ERR_INVALID, "instance[" + std::to_string(i) + "] = " + std::to_string(instance[i]) +
+                                                    " is outside -1 .. " + std::to_string(ni - 1));
+    }
+    return query_host(c, n, rays, instance, hits, false);
+}
+
+int jt_occluded(jt_ctx* c, int64_t n, const float* rays, uint8_t* occluded) {
+    bool done;
+    if (const int st = query_check(c, n, rays, "rays", occluded, "occluded", &done)) return st;
+    return done ? JT_OK : query_host(c, n, rays, nullptr, occluded, true);
+}
+
+}  // extern "C"

@@ -279,6 +279,7 @@ void jt_destroy(jt_ctx* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->stream2) (void)hipStreamSynchronize(c->stream2);
     for (void* p : c->allocations) (void)hipFree(p);
+    query_free(c);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     for (int k = 0; k < 2; k++) {
@@ -311,6 +312,7 @@ int jt_create(const jt_scene* scene, const jt_scene_bvh* bvh, const jt_lights* l
     c->sampler = params->sampler;
     c->choice = ps.choice;
     c->env_alias = ps.hs.env_alias;
+    c->inst_new = ps.hs.inst_new;  // the ray queries' instance numbering (jt_intersect.hip)
     auto bail = [&](int status) {
         jt_destroy(c);
         return status;

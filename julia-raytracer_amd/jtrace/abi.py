@@ -148,7 +148,16 @@ class jt_denoise_guided_params(C.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class jt_hit(C.Structure):
+    _fields_ = [("instance", C.c_int32), ("element", C.c_int32), ("u", C.c_float), ("v", C.c_float),
+                ("t", C.c_float), ("hit", C.c_int32)]
+
+
+# jt_hit as a numpy record (TraceState.intersect returns an array of these)
+HIT_DTYPE = np.dtype([("instance", "<i4"), ("element", "<i4"), ("u", "<f4"), ("v", "<f4"), ("t", "<f4"), ("hit", "<i4")])
+
 assert C.sizeof(jt_bvh_node) == 32
+assert C.sizeof(jt_hit) == 24 == HIT_DTYPE.itemsize
 
 
 def _ptr(arr: np.ndarray | None, ctype):
@@ -303,6 +312,10 @@ def _declare(lib):
     lib.jt_get_noise.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     lib.jt_adapt.argtypes = [C.c_void_p, C.c_double, i32p]
     lib.jt_get_sample_counts.argtypes = [C.c_void_p, i32p]
+    lib.jt_intersect.argtypes = [C.c_void_p, C.c_int64, f32p, i32p, C.POINTER(jt_hit)]
+    lib.jt_occluded.argtypes = [C.c_void_p, C.c_int64, f32p, u8p]
+    lib.jt_intersect_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.jt_occluded_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     lib.jt_reset.argtypes = [C.c_void_p]
     lib.jt_get_device_buffers.argtypes = [C.c_void_p, C.POINTER(jt_device_buffers)]
     lib.jt_set_counters.argtypes = [C.c_void_p, C.c_int32]
@@ -321,7 +334,7 @@ EXPORTED_SYMBOLS = [
     "jt_get_aovs", "jt_get_counters", "jt_reset", "jt_get_device_buffers", "jt_set_counters", "jt_describe", "jt_synchronize",
     "jt_destroy", "jt_denoise_defaults", "jt_denoise", "jt_get_denoised", "jt_denoise_image",
     "jt_get_variance", "jt_get_noise", "jt_denoise_guided_defaults", "jt_denoise_guided", "jt_denoise_guided_image",
-    "jt_adapt", "jt_get_sample_counts",
+    "jt_adapt", "jt_get_sample_counts", "jt_intersect", "jt_occluded", "jt_intersect_device", "jt_occluded_device",
 ]
 
 

@@ -12,6 +12,8 @@
                                                        -> jt_denoise_guided, jt_denoise_guided_image,
                                                        jt_denoise_guided_defaults
     state.adapt() / state.sample_counts() (the build's own) -> jt_adapt, jt_get_sample_counts
+    state.intersect() / state.occluded()   src/bvh.jl:306 -> jt_intersect, jt_occluded (and their
+                                                       device-pointer variants for torch tensors)
 
 There is no CPU fallback anywhere in this module: every call goes through libjtrace_hip.so.
 """
@@ -213,6 +215,65 @@ class TraceState:
         abi.check(self.lib, self.lib.jt_get_sample_counts(self.handle, out.ctypes.data_as(abi.i32p)))
         return out
 
+    # --- ray queries (jt_intersect, jt_occluded: include/jtrace.h)
+    def _device_rays(self, rays, instance=None):
+        """A torch tensor of rays (and of instance ids) checked for the zero-copy path: (torch, n)."""
+        import torch
+        dev = int(self.params.device)
+        if self.devices is not None:
+            raise abi.JTError(-2, "ray queries are not available on a multi-device context")
+        for name, t, dtype, shape in (("rays", rays, torch.float32, (len(rays), 6)),
+                                      ("instance", instance, torch.int32, (len(rays),))):
+            if t is None:
+                continue
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device.index == dev and t.dtype == dtype
+                    and tuple(t.shape) == shape and t.is_contiguous()):
+                raise ValueError(f"{name}: expected a contiguous {dtype} tensor of shape {shape} on cuda:{dev}")
+        # the library reads on the context's own stream: what produced the tensors must be done
+        torch.cuda.current_stream(dev).synchronize()
+        return torch, len(rays)
+
+    def intersect(self, rays, instance=None):
+        """jt_intersect: the closest hit of every ray (n, 6) = (origin, direction) on the context's
+        scene, in the context's traversal; instance: None, or per ray -1 (the scene) or an
+        instance id (that instance only). A float32 numpy array gives a structured array with
+        jt_hit's fields (abi.HIT_DTYPE); a torch tensor on the context's device goes zero-copy
+        through jt_intersect_device and gives an int32 (n, 6) tensor of the records (split_hits
+        names the fields)."""
+        if hasattr(rays, "data_ptr"):
+            torch, n = self._device_rays(rays, instance)
+            out = torch.empty((n, 6), dtype=torch.int32, device=rays.device)
+            abi.check(self.lib, self.lib.jt_intersect_device(self.handle, n, rays.data_ptr(),
+                                                             None if instance is None else instance.data_ptr(),
+                                                             out.data_ptr()))
+            return out
+        rays = _host_rays(rays)
+        n = len(rays)
+        ip = None
+        if instance is not None:
+            instance = np.ascontiguousarray(instance, np.int32)
+            if instance.shape != (n,):
+                raise ValueError(f"instance: expected shape ({n},), got {instance.shape}")
+            ip = instance.ctypes.data_as(abi.i32p)
+        out = np.empty(n, abi.HIT_DTYPE)
+        abi.check(self.lib, self.lib.jt_intersect(self.handle, n, rays.ctypes.data_as(abi.f32p), ip,
+                                                  out.ctypes.data_as(C.POINTER(abi.jt_hit))))
+        return out
+
+    def occluded(self, rays):
+        """jt_occluded: bool (n,), whether anything is hit along each ray (a numpy array, or for a
+        torch tensor on the context's device a torch.bool tensor there, zero-copy)."""
+        if hasattr(rays, "data_ptr"):
+            torch, n = self._device_rays(rays)
+            out = torch.empty(n, dtype=torch.uint8, device=rays.device)
+            abi.check(self.lib, self.lib.jt_occluded_device(self.handle, n, rays.data_ptr(), out.data_ptr()))
+            return out != 0
+        rays = _host_rays(rays)
+        out = np.empty(len(rays), np.uint8)
+        abi.check(self.lib, self.lib.jt_occluded(self.handle, len(rays), rays.ctypes.data_as(abi.f32p),
+                                                 out.ctypes.data_as(abi.u8p)))
+        return out != 0
+
     def counters(self) -> dict:
         c = abi.jt_counters()
         abi.check(self.lib, self.lib.jt_get_counters(self.handle, C.byref(c)))
@@ -266,6 +327,23 @@ def trace_samples(state: TraceState):
 
 def get_image(state: TraceState) -> np.ndarray:
     return state.get_image()
+
+
+def _host_rays(rays) -> np.ndarray:
+    rays = np.ascontiguousarray(rays, np.float32)
+    if rays.ndim != 2 or rays.shape[1] != 6:
+        raise ValueError(f"rays: expected shape (n, 6) = (origin, direction), got {rays.shape}")
+    return rays
+
+
+def split_hits(records) -> dict:
+    """The fields of TraceState.intersect's records, by name: a structured numpy array, or the
+    int32 (n, 6) torch tensor of the device path (u, v, t reinterpreted as float32, no copy)."""
+    if isinstance(records, np.ndarray):
+        return {name: records[name] for name in abi.HIT_DTYPE.names}
+    import torch
+    return {name: records[:, k].view(torch.float32) if name in ("u", "v", "t") else records[:, k]
+            for k, name in enumerate(abi.HIT_DTYPE.names)}
 
 
 def _with_overrides(params, overrides):
