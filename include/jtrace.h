@@ -25,6 +25,9 @@
  *                      target take no more samples; jt_get_sample_counts the samples per pixel
  *   jt_intersect       ~ intersect_scene_bvh / intersect_instance_bvh (src/bvh.jl:306-520) for the
  *                      caller's own rays on the context's scene; jt_occluded its find_any form
+ *   jt_eval_hits       ~ eval_shading_position / eval_shading_normal / eval_material (src/scene.jl:416-673)
+ *                      at the caller's hit records; jt_camera_rays ~ sample_camera (src/trace.jl:651-674);
+ *                      jt_gbuffer the two around jt_intersect: the surface under every pixel
  *   jt_destroy / jt_last_error — lifetime and error reporting (the reference throws Julia exceptions)
  *
  * Host helpers (run on the CPU, no device needed) that restate the reference's host code
@@ -589,6 +592,69 @@ int jt_intersect(jt_ctx* ctx, int64_t n, const float* rays /* n x (o, d), 6 floa
 int jt_occluded(jt_ctx* ctx, int64_t n, const float* rays, uint8_t* occluded /* n */);
 int jt_intersect_device(jt_ctx* ctx, int64_t n, const void* d_rays, const void* d_instance, void* d_hits);
 int jt_occluded_device(jt_ctx* ctx, int64_t n, const void* d_rays, void* d_occluded);
+
+/* ---- the surface at a hit ---------------------------------------------------------------- */
+/* What the integrator evaluates at a hit (src/scene.jl eval_shading_position, eval_shading_normal,
+ * eval_material) and the camera ray it starts from (src/trace.jl sample_camera), for the caller's
+ * own records: the position or normal under a pixel, noise-free albedo, normal and depth guide
+ * images, baking, probe placement, picking. */
+typedef struct jt_surface {   /* 96 bytes, 24 words */
+    float position[3];   /* eval_shading_position: the element's interpolated point, in world space */
+    float normal[3];     /* eval_shading_normal with outgoing = -d: normal map / vertex normals / element
+                            normal, flipped to face -d unless the material is refractive: the
+                            integrator's `normal`, the normal AOV's value */
+    float gnormal[3];    /* eval_element_normal, never flipped */
+    float texcoord[2];   /* eval_texcoord (u, v where the shape has none) */
+    float opacity;
+    float color[3];      /* material.color * colour texture * vertex colour: the albedo AOV's value */
+    float roughness;     /* the material point's: squared, then clamped / zeroed by type (eval_material) */
+    float emission[3];
+    float metallic;
+    int32_t material;    /* index into jt_scene.materials */
+    int32_t type;        /* jt_material_type */
+    float ior;
+    int32_t hit;         /* 1 / 0; on 0 every other word is 0 */
+} jt_surface;
+/* jt_eval_hits: for record i the surface hits[i] names, as seen along rays[i] (rays as in
+ * jt_intersect, n x (o, d)). Only the ray's direction is read and it need not be normalised: it
+ * enters through the sign of dot(normal, -d) alone. Instances are numbered as in
+ * jt_scene.instances, as in jt_hit. The record is a miss record (all 24 words zero) when
+ * hits[i].hit == 0, when the instance is outside 0 .. ninstances-1, when the element is outside
+ * the shape's elements, or when u or v is not finite: the kernel checks these before it loads
+ * anything the record names, so it stays inside the scene's arrays for any input. A finite uv
+ * outside the element is evaluated as given. Every value has the bits the integrator computes
+ * at that hit.
+ * jt_camera_rays: the W*H camera rays (o, d), row-major pixels. sample >= 0: the ray the
+ * integrator traces for (pixel, sample) — the sample's random stream, its four draws, the tent
+ * filter if the context has it, the lens sample — bit for bit; sample is not bounded by
+ * params.samples. sample == -1: the deterministic ray through the pixel centre, image uv
+ * ((i + 0.5f) / W, (j + 0.5f) / H), lens uv (0, 0), no filter. A context with a tile share still
+ * produces every pixel.
+ * jt_gbuffer: jt_camera_rays, then jt_intersect_device of those rays (scene queries, the
+ * context's traversal, the tie re-run included), then jt_eval_hits, in stream order on buffers
+ * the context owns; rays and hits are copied out where not NULL. It returns the bits those three
+ * calls give. It reports the first geometric hit: the integrator passes through a surface with
+ * probability 1 - opacity, the G-buffer never does, so where opacity < 1 the integrator's AOVs
+ * can be those of a surface behind.
+ * The *_device variants take device pointers on the context's device, run on the context's
+ * stream and return when it is idle; d_hits must be aligned to 8 bytes, d_out and d_surfaces to
+ * 16, d_rays to 8 where rays are written (any device allocation is; JT_ERR_INVALID otherwise).
+ * The host variants stage through buffers the context owns, as the ray queries do. All of this reads the scene and the parameters only: image, AOVs, stream
+ * means, variance, the adaptive mask and every jt_counters field stay bit for bit as they were,
+ * queued samples stay queued.
+ * Errors, in this order: JT_ERR_INVALID (naming the argument) for a NULL ctx, rays, hits or
+ * output, n < 0 or n > 2^30, sample < -1, a misaligned device pointer, before the context is looked
+ * at and before anything is written; n == 0 returns JT_OK
+ * with no device work; JT_ERR_UNSUPPORTED for a multi-device context; JT_ERR_STATE for a failed
+ * context. */
+int jt_eval_hits(jt_ctx* ctx, int64_t n, const float* rays /* n x 6 */, const jt_hit* hits, jt_surface* out);
+int jt_camera_rays(jt_ctx* ctx, int32_t sample, float* rays /* W*H x 6, row-major pixels */);
+int jt_gbuffer(jt_ctx* ctx, int32_t sample, float* rays /* W*H x 6, may be NULL */, jt_hit* hits /* W*H, may be NULL */,
+               jt_surface* surfaces /* W*H */);
+int jt_eval_hits_device(jt_ctx* ctx, int64_t n, const void* d_rays, const void* d_hits, void* d_out);
+int jt_camera_rays_device(jt_ctx* ctx, int32_t sample, void* d_rays);
+int jt_gbuffer_device(jt_ctx* ctx, int32_t sample, void* d_rays /* may be NULL */, void* d_hits /* may be NULL */,
+                      void* d_surfaces);
 
 /* zero accumulators (at once if their device pointers were handed out, else before they are
  * next read or overwritten), samples = 0, queued samples dropped */

@@ -1,7 +1,7 @@
 // jt_context.h — the device context behind include/jtrace.h's jt_ctx and the few functions its
 // pieces share: jt_trace.hip (creation, the sample queue, the getters), jt_multi.hip (the
-// multi-device context), jt_denoise.hip, jt_error.hip, jt_adapt.hip and jt_intersect.hip (their
-// context halves). Not part of the ABI.
+// multi-device context), jt_denoise.hip, jt_error.hip, jt_adapt.hip, jt_intersect.hip and
+// jt_surface.hip (their context halves). Not part of the ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -100,15 +100,22 @@ struct jt_ctx {
     // `allocations`: that permutation and its inverse, and the launch's ray counter. q_grow: the
     // buffers that grow with the calls — the query grid's own stack overflow area (q_ovf_entries
     // ints) and the host variants' staging of rays, instance ids and results (q_stage_rays
-    // rays) — kept across jt_reset, freed by jt_destroy (query_free)
+    // rays) — kept across jt_reset, freed by jt_destroy (query_free). The surface calls
+    // (jt_eval_hits, jt_camera_rays, jt_gbuffer; jt_surface.hip) stage rays and hits in the same
+    // buffers and their jt_surface records in Q_SURF (q_stage_surf records)
     std::vector<int> inst_new;
     int* q_to_dev = nullptr;
     int* q_to_ref = nullptr;
     unsigned* q_counter = nullptr;
-    enum { Q_OVF = 0, Q_RAYS, Q_INST, Q_OUT, Q_NGROW };
-    void* q_grow[Q_NGROW] = {nullptr, nullptr, nullptr, nullptr};
+    enum { Q_OVF = 0, Q_RAYS, Q_INST, Q_OUT, Q_SURF, Q_NGROW };
+    void* q_grow[Q_NGROW] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     size_t q_ovf_entries = 0;
     long long q_stage_rays = 0;
+    long long q_stage_surf = 0;
+    // inst_nelem: the elements of each instance's shape, in the caller's numbering (jt_create);
+    // uploaded by the first surface call (s_nelem, in `allocations`): surface_kernel's range check
+    std::vector<int> inst_nelem;
+    int* s_nelem = nullptr;
 
     // ---- a multi-device context (jt_create_multi) owns its sub-contexts and reduce state here
     // and uses, of the fields above, only the size, the sample counts, the queue, `failed`,
@@ -135,6 +142,13 @@ int trace_finish(jt_ctx* c, float* ms);
 int flush(jt_ctx* c);
 // frees the ray queries' growing buffers (jt_ctx::q_grow; jt_intersect.hip), for jt_destroy
 void query_free(jt_ctx* c);
+// the ray queries' pieces the surface calls share (jt_intersect.hip). query_setup: the first call's
+// uploads (q_to_dev, q_to_ref, q_counter). query_grow: buffer `which` of q_grow replaced by one of
+// at least `bytes` (its content is not kept); JT_ERR_NOMEM "hipMalloc <what>". query_stage: the
+// staging of rays, instance ids and jt_hit records grown to hold n rays
+int query_setup(jt_ctx* c);
+int query_grow(jt_ctx* c, int which, size_t bytes, const char* what);
+int query_stage(jt_ctx* c, int64_t n);
 
 // xyz of np float4 to np x 3 floats (the AOV getters)
 inline void unpack3(const std::vector<float4>& src, float* dst) {

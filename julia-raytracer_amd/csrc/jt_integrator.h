@@ -563,12 +563,11 @@ __device__ __forceinline__ void eval_camera(const DCamera& cam, v2 image_uv, v2 
     }
 }
 
-// trace_sample prologue (src/trace.jl:597-608): 4 draws, camera ray (sample_camera :651-674)
-template <int F>
-__device__ __forceinline__ void start_path(const DParams& P, int i, int j, int pixel, int sample, Path& st) {
-    st.rng = rng_init(P.seed, pixel, sample);
-    v2 puv = rand2f(st.rng);
-    v2 luv = rand2f(st.rng);
+// sample_camera (src/trace.jl:651-674) after the prologue's 4 draws (:597-608): the camera ray of
+// pixel (i, j) from an rng at the start of the sample's stream (also camera_kernel, jt_surface.hip)
+__device__ __forceinline__ void camera_sample(const DParams& P, int i, int j, Rng& rng, v3& o, v3& d) {
+    v2 puv = rand2f(rng);
+    v2 luv = rand2f(rng);
     v2 uv;
     if (!P.tentfilter) {
         uv = V2(((float)i + puv.x) / (float)P.width, ((float)j + puv.y) / (float)P.height);
@@ -578,7 +577,14 @@ __device__ __forceinline__ void start_path(const DParams& P, int i, int j, int p
                     width * (puv.y < 0.5f ? __builtin_sqrtf(2 * puv.y) - 1 : 1 - __builtin_sqrtf(2 - 2 * puv.y)) + offset);
         uv = V2(((float)i + fuv.x) / (float)P.width, ((float)j + fuv.y) / (float)P.height);
     }
-    eval_camera(P.cam, uv, P.cam.pinhole ? sample_disk_signs(luv) : sample_disk(luv), st.o, st.d);
+    eval_camera(P.cam, uv, P.cam.pinhole ? sample_disk_signs(luv) : sample_disk(luv), o, d);
+}
+
+// trace_sample prologue (src/trace.jl:597-608): 4 draws, camera ray
+template <int F>
+__device__ __forceinline__ void start_path(const DParams& P, int i, int j, int pixel, int sample, Path& st) {
+    st.rng = rng_init(P.seed, pixel, sample);
+    camera_sample(P, i, j, st.rng, st.o, st.d);
     st.set_radiance<F>(V3(0, 0, 0));
     st.set_weight<F>(V3(1, 1, 1));
     st.set_max_roughness<F>(0.0f);

@@ -155,40 +155,6 @@ void launch_query(int grid, hipStream_t stream, const DScene& S, const jtk::DQue
     hipLaunchKernelGGL((jtk::query_kernel<WIDE, OVF, ANY>), dim3((unsigned)grid), dim3(BLOCK), 0, stream, S, Q);
 }
 
-// a buffer of jt_ctx::q_grow of at least `bytes` (the old one is freed first: its content is not kept)
-int grow(jt_ctx* c, int which, size_t bytes, const char* what) {
-    if (c->q_grow[which]) (void)hipFree(c->q_grow[which]);
-    c->q_grow[which] = nullptr;
-    if (hipMalloc(&c->q_grow[which], bytes) != hipSuccess) {
-        c->q_grow[which] = nullptr;
-        (void)hipGetLastError();
-        return jt::fail(JT_ERR_NOMEM, std::string("hipMalloc ") + what);
-    }
-    return JT_OK;
-}
-
-// the first query's uploads: the instance permutation both ways and the ray counter
-int query_setup(jt_ctx* c) {
-    if (c->q_counter) return JT_OK;
-    const size_t ni = c->inst_new.size();
-    std::vector<int> to_ref(ni, -1);
-    for (size_t k = 0; k < ni; k++) to_ref[(size_t)c->inst_new[k]] = (int)k;
-    void *a = nullptr, *b = nullptr, *w = nullptr;
-    int st;
-    const size_t bytes = (ni ? ni : 1) * sizeof(int);
-    if ((st = device_alloc(c, bytes, "query instance ids", &a)) || (st = device_alloc(c, bytes, "query instance ids", &b)) ||
-        (st = device_alloc(c, sizeof(unsigned), "query ray counter", &w)))
-        return st;
-    hipError_t e;
-    if (ni && ((e = hipMemcpy(a, c->inst_new.data(), bytes, hipMemcpyHostToDevice)) != hipSuccess ||
-               (e = hipMemcpy(b, to_ref.data(), bytes, hipMemcpyHostToDevice)) != hipSuccess))
-        return hip_fail(e, "hipMemcpy query instance ids");
-    c->q_to_dev = (int*)a;
-    c->q_to_ref = (int*)b;
-    c->q_counter = (unsigned*)w;
-    return JT_OK;
-}
-
 // the checks every entry point shares, in the header's order; *done: n == 0, nothing to do
 int query_check(const jt_ctx* c, int64_t n, const void* rays, const char* rays_name, const void* out, const char* out_name,
                 bool* done) {
@@ -226,7 +192,7 @@ int query_run(jt_ctx* c, int64_t n, const void* d_rays, const void* d_inst, void
         const size_t entries = jtq::query_ovf_entries(grid, need);
         if (entries > c->q_ovf_entries) {
             c->q_ovf_entries = 0;
-            if ((st = grow(c, jt_ctx::Q_OVF, entries * sizeof(int), "query stack overflow")) != JT_OK) return st;
+            if ((st = query_grow(c, jt_ctx::Q_OVF, entries * sizeof(int), "query stack overflow")) != JT_OK) return st;
             c->q_ovf_entries = entries;
         }
         S.ovf = (int*)c->q_grow[jt_ctx::Q_OVF];
@@ -268,16 +234,7 @@ int query_run(jt_ctx* c, int64_t n, const void* d_rays, const void* d_inst, void
 int query_host(jt_ctx* c, int64_t n, const float* rays, const int32_t* instance, void* out, bool any) {
     (void)hipSetDevice(c->device);
     const size_t N = (size_t)n;
-    if (n > c->q_stage_rays) {
-        const size_t cap = (size_t)jtq::query_stage_rays(c->q_stage_rays, n);
-        c->q_stage_rays = 0;
-        int st;
-        if ((st = grow(c, jt_ctx::Q_RAYS, cap * 6 * sizeof(float), "query rays")) ||
-            (st = grow(c, jt_ctx::Q_INST, cap * sizeof(int32_t), "query instance ids")) ||
-            (st = grow(c, jt_ctx::Q_OUT, cap * sizeof(jt_hit), "query results")))
-            return st;
-        c->q_stage_rays = (long long)cap;
-    }
+    if (const int st = query_stage(c, n)) return st;
     void* const d_rays = c->q_grow[jt_ctx::Q_RAYS];
     void* const d_inst = instance ? c->q_grow[jt_ctx::Q_INST] : nullptr;
     void* const d_out = c->q_grow[jt_ctx::Q_OUT];
@@ -294,6 +251,54 @@ int query_host(jt_ctx* c, int64_t n, const float* rays, const int32_t* instance,
 
 }  // namespace
 
+// a buffer of jt_ctx::q_grow of at least `bytes` (the old one is freed first: its content is not kept)
+int jtc::query_grow(jt_ctx* c, int which, size_t bytes, const char* what) {
+    if (c->q_grow[which]) (void)hipFree(c->q_grow[which]);
+    c->q_grow[which] = nullptr;
+    if (hipMalloc(&c->q_grow[which], bytes) != hipSuccess) {
+        c->q_grow[which] = nullptr;
+        (void)hipGetLastError();
+        return jt::fail(JT_ERR_NOMEM, std::string("hipMalloc ") + what);
+    }
+    return JT_OK;
+}
+
+// the first query's uploads: the instance permutation both ways and the ray counter
+int jtc::query_setup(jt_ctx* c) {
+    if (c->q_counter) return JT_OK;
+    const size_t ni = c->inst_new.size();
+    std::vector<int> to_ref(ni, -1);
+    for (size_t k = 0; k < ni; k++) to_ref[(size_t)c->inst_new[k]] = (int)k;
+    void *a = nullptr, *b = nullptr, *w = nullptr;
+    int st;
+    const size_t bytes = (ni ? ni : 1) * sizeof(int);
+    if ((st = device_alloc(c, bytes, "query instance ids", &a)) || (st = device_alloc(c, bytes, "query instance ids", &b)) ||
+        (st = device_alloc(c, sizeof(unsigned), "query ray counter", &w)))
+        return st;
+    hipError_t e;
+    if (ni && ((e = hipMemcpy(a, c->inst_new.data(), bytes, hipMemcpyHostToDevice)) != hipSuccess ||
+               (e = hipMemcpy(b, to_ref.data(), bytes, hipMemcpyHostToDevice)) != hipSuccess))
+        return hip_fail(e, "hipMemcpy query instance ids");
+    c->q_to_dev = (int*)a;
+    c->q_to_ref = (int*)b;
+    c->q_counter = (unsigned*)w;
+    return JT_OK;
+}
+
+// the host variants' staging of rays, instance ids and jt_hit records, grown to hold n rays
+int jtc::query_stage(jt_ctx* c, int64_t n) {
+    if (n <= c->q_stage_rays) return JT_OK;
+    const size_t cap = (size_t)jtq::query_stage_rays(c->q_stage_rays, n);
+    c->q_stage_rays = 0;
+    int st;
+    if ((st = query_grow(c, jt_ctx::Q_RAYS, cap * 6 * sizeof(float), "query rays")) ||
+        (st = query_grow(c, jt_ctx::Q_INST, cap * sizeof(int32_t), "query instance ids")) ||
+        (st = query_grow(c, jt_ctx::Q_OUT, cap * sizeof(jt_hit), "query results")))
+        return st;
+    c->q_stage_rays = (long long)cap;
+    return JT_OK;
+}
+
 void jtc::query_free(jt_ctx* c) {
     for (void*& p : c->q_grow) {
         if (p) (void)hipFree(p);
@@ -301,6 +306,7 @@ void jtc::query_free(jt_ctx* c) {
     }
     c->q_ovf_entries = 0;
     c->q_stage_rays = 0;
+    c->q_stage_surf = 0;
 }
 
 static_assert(sizeof(jt_hit) == 24, "the query kernel writes a jt_hit as six 32-bit words");

@@ -313,6 +313,11 @@ int jt_create(const jt_scene* scene, const jt_scene_bvh* bvh, const jt_lights* l
     c->choice = ps.choice;
     c->env_alias = ps.hs.env_alias;
     c->inst_new = ps.hs.inst_new;  // the ray queries' instance numbering (jt_intersect.hip)
+    c->inst_nelem.resize((size_t)scene->ninstances);  // and the surface calls' element ranges (jt_surface.hip)
+    for (int k = 0; k < scene->ninstances; k++) {
+        const jt_shape& sh = scene->shapes[scene->instances[k].shape];
+        c->inst_nelem[(size_t)k] = sh.ntriangles ? sh.ntriangles : sh.nquads;  // flatten_shape's kind
+    }
     auto bail = [&](int status) {
         jt_destroy(c);
         return status;

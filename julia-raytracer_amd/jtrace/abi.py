@@ -156,8 +156,22 @@ class jt_hit(C.Structure):
 # jt_hit as a numpy record (TraceState.intersect returns an array of these)
 HIT_DTYPE = np.dtype([("instance", "<i4"), ("element", "<i4"), ("u", "<f4"), ("v", "<f4"), ("t", "<f4"), ("hit", "<i4")])
 
+
+class jt_surface(C.Structure):
+    _fields_ = [("position", C.c_float * 3), ("normal", C.c_float * 3), ("gnormal", C.c_float * 3),
+                ("texcoord", C.c_float * 2), ("opacity", C.c_float), ("color", C.c_float * 3),
+                ("roughness", C.c_float), ("emission", C.c_float * 3), ("metallic", C.c_float),
+                ("material", C.c_int32), ("type", C.c_int32), ("ior", C.c_float), ("hit", C.c_int32)]
+
+
+# jt_surface as a numpy record (TraceState.surfaces returns an array of these)
+SURFACE_DTYPE = np.dtype([("position", "<f4", 3), ("normal", "<f4", 3), ("gnormal", "<f4", 3), ("texcoord", "<f4", 2),
+                          ("opacity", "<f4"), ("color", "<f4", 3), ("roughness", "<f4"), ("emission", "<f4", 3),
+                          ("metallic", "<f4"), ("material", "<i4"), ("type", "<i4"), ("ior", "<f4"), ("hit", "<i4")])
+
 assert C.sizeof(jt_bvh_node) == 32
 assert C.sizeof(jt_hit) == 24 == HIT_DTYPE.itemsize
+assert C.sizeof(jt_surface) == 96 == SURFACE_DTYPE.itemsize
 
 
 def _ptr(arr: np.ndarray | None, ctype):
@@ -316,6 +330,12 @@ def _declare(lib):
     lib.jt_occluded.argtypes = [C.c_void_p, C.c_int64, f32p, u8p]
     lib.jt_intersect_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.jt_occluded_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    lib.jt_eval_hits.argtypes = [C.c_void_p, C.c_int64, f32p, C.POINTER(jt_hit), C.POINTER(jt_surface)]
+    lib.jt_camera_rays.argtypes = [C.c_void_p, C.c_int32, f32p]
+    lib.jt_gbuffer.argtypes = [C.c_void_p, C.c_int32, f32p, C.POINTER(jt_hit), C.POINTER(jt_surface)]
+    lib.jt_eval_hits_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.jt_camera_rays_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    lib.jt_gbuffer_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.jt_reset.argtypes = [C.c_void_p]
     lib.jt_get_device_buffers.argtypes = [C.c_void_p, C.POINTER(jt_device_buffers)]
     lib.jt_set_counters.argtypes = [C.c_void_p, C.c_int32]
@@ -335,6 +355,7 @@ EXPORTED_SYMBOLS = [
     "jt_destroy", "jt_denoise_defaults", "jt_denoise", "jt_get_denoised", "jt_denoise_image",
     "jt_get_variance", "jt_get_noise", "jt_denoise_guided_defaults", "jt_denoise_guided", "jt_denoise_guided_image",
     "jt_adapt", "jt_get_sample_counts", "jt_intersect", "jt_occluded", "jt_intersect_device", "jt_occluded_device",
+    "jt_eval_hits", "jt_camera_rays", "jt_gbuffer", "jt_eval_hits_device", "jt_camera_rays_device", "jt_gbuffer_device",
 ]
 
 

@@ -274,6 +274,79 @@ class TraceState:
                                                  out.ctypes.data_as(abi.u8p)))
         return out != 0
 
+    # --- the surface at a hit (jt_eval_hits, jt_camera_rays, jt_gbuffer: include/jtrace.h)
+    def _torch_device(self):
+        """torch and the context's device, for the calls that return device tensors."""
+        import torch
+        if self.devices is not None:
+            raise abi.JTError(-2, "surface evaluation and camera rays are not available on a multi-device context")
+        dev = int(self.params.device)
+        torch.cuda.current_stream(dev).synchronize()
+        return torch, torch.device("cuda", dev)
+
+    def camera_rays(self, sample: int = -1, device: bool = False):
+        """jt_camera_rays: the (W*H, 6) float32 camera rays (origin, direction), row-major pixels.
+        sample >= 0: the ray the integrator traces for (pixel, sample), bit for bit; -1: the
+        deterministic ray through the pixel centre. device=True gives a torch tensor on the
+        context's device (jt_camera_rays_device), else a numpy array."""
+        n = self.width * self.height
+        if device:
+            torch, dev = self._torch_device()
+            out = torch.empty((n, 6), dtype=torch.float32, device=dev)
+            abi.check(self.lib, self.lib.jt_camera_rays_device(self.handle, int(sample), out.data_ptr()))
+            return out
+        out = np.empty((n, 6), np.float32)
+        abi.check(self.lib, self.lib.jt_camera_rays(self.handle, int(sample), out.ctypes.data_as(abi.f32p)))
+        return out
+
+    def surfaces(self, rays, hits):
+        """jt_eval_hits: the surface each hit record names, as seen along its ray: position,
+        shading and element normal, texture coordinates, the material point. numpy rays (n, 6)
+        and hits (abi.HIT_DTYPE) give a structured array (abi.SURFACE_DTYPE); torch tensors on the
+        context's device (rays float32 (n, 6), hits int32 (n, 6) as intersect returns them) go
+        zero-copy through jt_eval_hits_device and give a float32 (n, 24) tensor of the records
+        (split_surfaces names the fields)."""
+        if hasattr(rays, "data_ptr"):
+            torch, n = self._device_rays(rays)
+            if not (isinstance(hits, torch.Tensor) and hits.device == rays.device and hits.dtype == torch.int32
+                    and tuple(hits.shape) == (n, 6) and hits.is_contiguous()):
+                raise ValueError(f"hits: expected a contiguous int32 tensor of shape ({n}, 6) on {rays.device}")
+            out = torch.empty((n, 24), dtype=torch.float32, device=rays.device)
+            abi.check(self.lib, self.lib.jt_eval_hits_device(self.handle, n, rays.data_ptr(), hits.data_ptr(), out.data_ptr()))
+            return out
+        rays = _host_rays(rays)
+        n = len(rays)
+        hits = np.ascontiguousarray(hits)
+        if hits.dtype != abi.HIT_DTYPE or hits.shape != (n,):
+            raise ValueError(f"hits: expected shape ({n},) of abi.HIT_DTYPE, got {hits.shape} of {hits.dtype}")
+        out = np.empty(n, abi.SURFACE_DTYPE)
+        abi.check(self.lib, self.lib.jt_eval_hits(self.handle, n, rays.ctypes.data_as(abi.f32p),
+                                                  hits.ctypes.data_as(C.POINTER(abi.jt_hit)),
+                                                  out.ctypes.data_as(C.POINTER(abi.jt_surface))))
+        return out
+
+    def gbuffer(self, sample: int = -1, device: bool = False):
+        """jt_gbuffer: (rays, hits, surfaces) of every pixel, row-major — camera_rays(sample), their
+        closest hits in the context's traversal, and the surfaces there, with the bits of those
+        three calls. The first geometric hit is reported: a surface with opacity < 1 is never
+        passed through. device=True gives torch tensors on the context's device."""
+        n = self.width * self.height
+        if device:
+            torch, dev = self._torch_device()
+            rays = torch.empty((n, 6), dtype=torch.float32, device=dev)
+            hits = torch.empty((n, 6), dtype=torch.int32, device=dev)
+            surf = torch.empty((n, 24), dtype=torch.float32, device=dev)
+            abi.check(self.lib, self.lib.jt_gbuffer_device(self.handle, int(sample), rays.data_ptr(), hits.data_ptr(),
+                                                           surf.data_ptr()))
+            return rays, hits, surf
+        rays = np.empty((n, 6), np.float32)
+        hits = np.empty(n, abi.HIT_DTYPE)
+        surf = np.empty(n, abi.SURFACE_DTYPE)
+        abi.check(self.lib, self.lib.jt_gbuffer(self.handle, int(sample), rays.ctypes.data_as(abi.f32p),
+                                                hits.ctypes.data_as(C.POINTER(abi.jt_hit)),
+                                                surf.ctypes.data_as(C.POINTER(abi.jt_surface))))
+        return rays, hits, surf
+
     def counters(self) -> dict:
         c = abi.jt_counters()
         abi.check(self.lib, self.lib.jt_get_counters(self.handle, C.byref(c)))
@@ -344,6 +417,23 @@ def split_hits(records) -> dict:
     import torch
     return {name: records[:, k].view(torch.float32) if name in ("u", "v", "t") else records[:, k]
             for k, name in enumerate(abi.HIT_DTYPE.names)}
+
+
+def split_surfaces(records) -> dict:
+    """The fields of TraceState.surfaces' records, by name: a structured numpy array, or the
+    float32 (n, 24) torch tensor of the device path (material, type and hit reinterpreted as
+    int32, vectors as (n, 3) / (n, 2) column ranges, no copy)."""
+    if isinstance(records, np.ndarray):
+        return {name: records[name] for name in abi.SURFACE_DTYPE.names}
+    import torch
+    out, k = {}, 0
+    for name in abi.SURFACE_DTYPE.names:
+        dt, shape = abi.SURFACE_DTYPE[name].base, abi.SURFACE_DTYPE[name].shape
+        w = shape[0] if shape else 1
+        col = records[:, k:k + w] if shape else records[:, k]
+        out[name] = col.view(torch.int32) if dt.kind == "i" else col
+        k += w
+    return out
 
 
 def _with_overrides(params, overrides):
