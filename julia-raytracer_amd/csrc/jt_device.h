@@ -54,11 +54,63 @@ __device__ __forceinline__ float dot(v3 a, v3 b) { return (a.x * b.x + a.y * b.y
 __device__ __forceinline__ v3 cross(v3 a, v3 b) {  // src/math.jl:112
     return V3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x);
 }
+// sqrtf(x), correctly rounded like the compiler's expansion it replaces (16 VALU instructions a
+// site: a pre-scale for tiny inputs, v_sqrt_f32, both 1-ulp neighbours tested with an FMA residual,
+// a post-scale, the zero/inf class), as a shorter sequence for x in [2^-95, inf): the bits of such
+// an x lie in [JL_SQRT_LO, JL_SQRT_HI). Zeros, denormals, smaller normals (whose residual would
+// leave the normal range), inf, NaN and negatives take __builtin_sqrtf. sqrt_fast<FORM> are the
+// candidate sequences; scripts/exhaustive/sqrt_check.hip compares each of them and jl_sqrt itself
+// with __builtin_sqrtf over all 2^32 bit patterns on gfx950, and only a form with no mismatch in
+// the domain is used (JT_SQRT_FORM; 0: __builtin_sqrtf everywhere). All four passed; 1 is the shortest
+// (profiles/item_sqrt_rcp/sqrt_check.log, EXPERIMENTS.md).
+// Used by normalize, length, sample_disk and sample_triangle. The hemisphere sample and the lobe
+// terms of jt_bsdf.h keep __builtin_sqrtf: with jl_sqrt in sample_hemisphere_cos the cornellbox
+// kernel's counting twin spilled 10 VGPRs, not 5 (with these four sites: 2).
+#ifndef JT_SQRT_FORM
+#define JT_SQRT_FORM 1
+#endif
+constexpr unsigned JL_SQRT_LO = 0x10000000u;  // 2^-95
+constexpr unsigned JL_SQRT_HI = 0x7f800000u;  // +inf
+template <int FORM>
+__device__ __forceinline__ float sqrt_fast(float x) {
+    if constexpr (FORM == 1) {
+        // v_rsq_f32 and one coupled Newton step on the root
+        const float y = __builtin_amdgcn_rsqf(x);
+        const float s = x * y, h = 0.5f * y;
+        return __builtin_fmaf(__builtin_fmaf(-s, s, x), h, s);
+    } else if constexpr (FORM == 2) {
+        // v_sqrt_f32 and one FMA-residual correction, half the reciprocal root from v_rsq_f32
+        const float s = __builtin_amdgcn_sqrtf(x), h = 0.5f * __builtin_amdgcn_rsqf(x);
+        return __builtin_fmaf(__builtin_fmaf(-s, s, x), h, s);
+    } else if constexpr (FORM == 3) {
+        // the compiler's correction without its scaling and class handling: v_sqrt_f32 is within
+        // 1 ulp, so the root is it or a neighbour; the residuals' signs say which
+        const float s = __builtin_amdgcn_sqrtf(x);
+        const float dn = __uint_as_float(__float_as_uint(s) - 1u), up = __uint_as_float(__float_as_uint(s) + 1u);
+        const float rd = __builtin_fmaf(-dn, s, x), ru = __builtin_fmaf(-up, s, x);
+        const float t = rd <= 0.0f ? dn : s;
+        return ru > 0.0f ? up : t;
+    } else {
+        // v_rsq_f32, one Goldschmidt step on root and half reciprocal root, one residual correction
+        const float y = __builtin_amdgcn_rsqf(x);
+        float g = x * y, h = 0.5f * y;
+        const float e = __builtin_fmaf(-h, g, 0.5f);
+        h = __builtin_fmaf(h, e, h);
+        g = __builtin_fmaf(g, e, g);
+        return __builtin_fmaf(__builtin_fmaf(-g, g, x), h, g);
+    }
+}
+__device__ __forceinline__ float jl_sqrt(float x) {
+#if JT_SQRT_FORM
+    if (__builtin_expect(__float_as_uint(x) - JL_SQRT_LO < JL_SQRT_HI - JL_SQRT_LO, 1)) return sqrt_fast<JT_SQRT_FORM>(x);
+#endif
+    return __builtin_sqrtf(x);
+}
 __device__ __forceinline__ v3 normalize(v3 a) {  // src/math.jl:71-78
-    float l = __builtin_sqrtf(dot(a, a));
+    float l = jl_sqrt(dot(a, a));
     return l != 0 ? a / l : a;
 }
-__device__ __forceinline__ float length(v3 a) { return __builtin_sqrtf(dot(a, a)); }
+__device__ __forceinline__ float length(v3 a) { return jl_sqrt(dot(a, a)); }
 
 // Julia min/max for floats (base/math.jl): NaN-propagating, -0 < +0 — IEEE 754-2019
 // minimum/maximum, which gfx950 has as v_minimum3_f32 / v_maximum3_f32 (JT_NAN_PROP, one
@@ -104,6 +156,12 @@ __device__ __forceinline__ float jl_rcp(float x) {
     }
     return 1.0f / x;
 }
+// JT_RCP_WEIGHTS: the running-mean weights 1 / (c + 1) (Aov::w, stream_weight) and the Russian
+// roulette's 1 / rr_prob through jl_rcp instead of the division's full sequence; the same bits
+#ifndef JT_RCP_WEIGHTS
+#define JT_RCP_WEIGHTS 1
+#endif
+__device__ __forceinline__ float jl_rcp_weight(float x) { return JT_RCP_WEIGHTS ? jl_rcp(x) : 1.0f / x; }
 __device__ __forceinline__ int jl_clampi(int x, int lo, int hi) { return x > hi ? hi : (x < lo ? lo : x); }
 __device__ __forceinline__ float max3(v3 a) { return JT_NAN_PROP ? jl_max3(a.x, a.y, a.z) : jl_max(jl_max(a.x, a.y), a.z); }
 
@@ -278,7 +336,7 @@ __device__ __forceinline__ v2 rand2f(Rng& r) {
 
 // ------------------------------------------------------------------------------ sampling.jl
 __device__ __forceinline__ v2 sample_disk(v2 ruv) {  // src/sampling.jl:12-16
-    float r = __builtin_sqrtf(ruv.y);
+    float r = jl_sqrt(ruv.y);
     float phi = 2 * pif * ruv.x;
     float s, c;
     jl_sincos(phi, &s, &c);
@@ -347,7 +405,8 @@ __device__ __forceinline__ float sample_discrete_pdf(const float* cdf, int idx1)
     return idx1 == 1 ? cdf[0] : cdf[idx1 - 1] - cdf[idx1 - 2];
 }
 __device__ __forceinline__ v2 sample_triangle(v2 ruv) {  // :58
-    return V2(1 - __builtin_sqrtf(ruv.x), ruv.y * __builtin_sqrtf(ruv.x));
+    const float r = jl_sqrt(ruv.x);
+    return V2(1 - r, ruv.y * r);
 }
 
 // ------------------------------------------------------------------------------ geometry.jl

@@ -186,7 +186,7 @@ __device__ __forceinline__ bool after_weight(const DParams& P, Path& st) {
     if (st.bounce() > 3) {
         float rr_prob = jl_min(0.99f, max3(st.weight<F>()));
         if (rand1f(st.rng) >= rr_prob) return true;
-        st.set_weight<F>(st.weight<F>() * (1 / rr_prob));
+        st.set_weight<F>(st.weight<F>() * jl_rcp_weight(rr_prob));
     }
     return next_bounce(P, st);
 }
@@ -367,7 +367,7 @@ struct Aov {
     template <int F>
     __device__ __forceinline__ float w() const {
         if (!lane_lds(F)) return w_;
-        if (ft_none(F)) return 1.0f / (float)(((reinterpret_cast<const int*>(acc)[11 * BLOCK] - first_) >> lk_) + 1);
+        if (ft_none(F)) return jl_rcp_weight((float)(((reinterpret_cast<const int*>(acc)[11 * BLOCK] - first_) >> lk_) + 1));
         return acc[12 * BLOCK];
     }
 };

@@ -220,35 +220,54 @@ template <bool WIDE, int F>
 __host__ __device__ constexpr bool item_first_pop() {
     return JT_ITEM_FIRST_POP == 1 || (JT_ITEM_FIRST_POP == 2 && !WIDE && !ft_none(F));
 }
-// a lane's item: the pixel's slot tile * 64 + l (l: pixel of the 8x8 tile; jt_create keeps
-// tiles below 2^20); ITEM_NONE: no pixel. The item's stream and sample live in the lane's LDS
-// slot [11] (its current global sample).
-constexpr unsigned ITEM_NONE = 0xffffffffu;
-
-// the image index of an item's pixel (its slot holds the global tile and the pixel of the tile)
+// a lane's item: its pixel's image coordinates, (j << 16) | i (item_encode, jt_plan.h; jt_create
+// keeps width and height within JT_ITEM_MAX_DIM); ITEM_NONE: no pixel. The item's stream and sample
+// live in the lane's LDS slot [11] (its current global sample). The hand-out has i and j in hand;
+// the sample start and the item's store take them back by shifts and masks, where recovering them
+// from tile * 64 + l took two divisions by the tile columns and two by the width each.
+// JT_ITEM_COORDS, measured against the tile form (three runs each, interleaved,
+// profiles/item_sqrt_rcp/ab_headline.txt, ab_others.txt): cornellbox +1.0 %; features2 1920x1080x64
+// -1.4 % (its kernel, which keeps the launch's arguments in registers, spilled 76 SGPRs instead of
+// 61), so the FT_MESH_ENV_QUAD kernels keep the tile form: the item is tile * 64 + l (jt_create
+// keeps tiles below 2^20), its pixel is item_pixel's.
+#ifndef JT_ITEM_COORDS
+#define JT_ITEM_COORDS 1
+#endif
+template <int F>
+__host__ __device__ constexpr bool item_coords() {
+    return JT_ITEM_COORDS && !mesh_env_quad_family(F);
+}
+// tile form: the image index of an item's pixel (its slot holds the global tile and the pixel of the tile)
 __device__ __forceinline__ int item_pixel(unsigned item, const DParams& P, int tiles_x) {
     const int t = (int)(item >> 6), l = (int)(item & 63u);
     return ((t / tiles_x) * 8 + (l >> 3)) * P.width + (t % tiles_x) * 8 + (l & 7);
 }
-// an item's slot among the launch's tiles (DAccum::part_*): tiles offset, offset + stride, ... are
-// launch tiles 0, 1, ...; (t - offset) / stride is exact, and t < 2^20 keeps the float quotient
-// within 2^-3 of it. Against the integer division: cornellbox +0.5 %, its 1/8 share +0.9 % (two
-// runs each, profiles/r06_ab/slot_float_vs_div_r06d.txt; the division's code raised the kernels'
-// spills from 1-2 to 4-6 VGPRs)
-__host__ __device__ __forceinline__ int item_slot(unsigned item, const DParams& P) {
-    const int t = (int)(item >> 6);
-    float inv = 1.0f / (float)P.tile_stride;
-#if defined(__HIP_DEVICE_COMPILE__)
-    // wave-uniform and loop-invariant: hoisted out of the persistent loop it held a VGPR for the
-    // whole kernel (the one the 96-VGPR cornellbox kernel spilled); as a scalar it costs none
-    inv = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(inv)));
-#endif
-    const int u = (int)((float)(t - P.tile_offset) * inv + 0.5f);
-    return u * 64 + (int)(item & 63u);
+// the item of pixel (i, j), pixel l of tile ut
+template <int F>
+__device__ __forceinline__ unsigned item_of(int ut, int l, int i, int j) {
+    return item_coords<F>() ? item_encode(i, j) : (unsigned)(ut * 64 + l);
+}
+// the image index of an item's pixel
+template <int F>
+__device__ __forceinline__ int item_pixel_index(unsigned item, const DParams& P, int tiles_x) {
+    return item_coords<F>() ? item_j(item) * P.width + item_i(item) : item_pixel(item, P, tiles_x);
+}
+// an item's slot among the launch's tiles (DAccum::part_*; item_slot, jt_plan.h): the inverse of
+// slot_pixel, with the host's reciprocal of the tile stride (DParams::tile_stride_rcp)
+template <int F>
+__device__ __forceinline__ int item_slot(unsigned item, const DParams& P) {
+    if constexpr (item_coords<F>()) return item_slot(item, (P.width + 7) >> 3, P.tile_offset, P.tile_stride_rcp);
+    else {
+        // the tile form computes the reciprocal itself, as a scalar (wave-uniform and loop-invariant:
+        // hoisted out of the persistent loop it would hold a VGPR for the whole kernel): with the
+        // host's, one more launch argument stayed live in this family's registers (features2 -0.7 %)
+        const float inv = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(1.0f / (float)P.tile_stride)));
+        return launch_tile((int)(item >> 6), P.tile_offset, inv) * 64 + (int)(item & 63u);
+    }
 }
 // running-mean weight of global sample s within its stream
 __device__ __forceinline__ float stream_weight(const DParams& P, int s) {
-    return 1.0f / (float)(((s - P.first) >> P.lk) + 1);
+    return jl_rcp_weight((float)(((s - P.first) >> P.lk) + 1));
 }
 
 #if JT_STAMPS
@@ -368,7 +387,7 @@ __device__ __forceinline__ void trace_body_items(const DScene& S0, const DParams
                 const int i = (ut % tiles_x) * 8 + (l & 7), j = (ut / tiles_x) * 8 + (l >> 3);
                 // a pixel outside the image (edge tiles) is skipped: the lane takes another
                 if (i < P.width && j < P.height) {
-                    item = (unsigned)(ut * 64 + l);
+                    item = item_of<F>(ut, l, i, j);
                     start = true;
                     const int s = JT_SB + uq;
                     acc_i[11 * BLOCK] = s;
@@ -383,7 +402,7 @@ __device__ __forceinline__ void trace_body_items(const DScene& S0, const DParams
                             h = (int)JT_A(hits)[pixel];
                         } else {
                             const size_t o = (size_t)((s - P.first) & (kstr - 1)) * (size_t)JT_A(nslot) +
-                                             (size_t)item_slot(item, P);
+                                             (size_t)item_slot<F>(item, P);
                             im = JT_A(part_img)[o];
                             al = JT_A(part_alb)[o];
                             nr = JT_A(part_nrm)[o];
@@ -410,10 +429,12 @@ __device__ __forceinline__ void trace_body_items(const DScene& S0, const DParams
         next_sample = false;
         if (start) {
             const int sample = acc_i[11 * BLOCK];
-            const int pixel = item_pixel(item, P, tiles_x);
+            const int tpixel = item_coords<F>() ? 0 : item_pixel(item, P, tiles_x);  // tile form
             if (!ft_none(F)) acc[12 * BLOCK] = stream_weight(P, sample);
             const DParams& P = karg_params<karg_params_on<SAMPLER, F>()>(P0);
-            start_path<F>(P, pixel % P.width, pixel / P.width, pixel, sample, st);
+            const int i = item_coords<F>() ? item_i(item) : tpixel % P.width;
+            const int j = item_coords<F>() ? item_j(item) : tpixel / P.width;
+            start_path<F>(P, i, j, item_coords<F>() ? j * P.width + i : tpixel, sample, st);
             query_start<WIDE>(S, T, st.o, st.d, -1, stack, 0, PB);
             if (!WC) lds_count(1, true);
             if constexpr (item_first_pop<WIDE, F>()) {
@@ -588,7 +609,7 @@ __device__ __forceinline__ void trace_body_items(const DScene& S0, const DParams
                 if (sample + kstr >= JT_SE) {
                     // the item is complete: store its stream's means (plain stores: no other item
                     // of this launch reads them; the combine kernel runs after the launch)
-                    const int pixel = item_pixel(item, P, tiles_x);
+                    const int pixel = item_pixel_index<F>(item, P, tiles_x);
                     const float4 im = make_float4(acc[0], acc[BLOCK], acc[2 * BLOCK], acc[3 * BLOCK]);
                     if (P.lk == 0) {
                         JT_A(image)[pixel] = im;
@@ -597,7 +618,7 @@ __device__ __forceinline__ void trace_body_items(const DScene& S0, const DParams
                         JT_A(hits)[pixel] = (long long)acc_i[10 * BLOCK];
                     } else {
                         const size_t o = (size_t)((sample - P.first) & (kstr - 1)) * (size_t)JT_A(nslot) +
-                                         (size_t)item_slot(item, P);
+                                         (size_t)item_slot<F>(item, P);
                         JT_A(part_img)[o] = im;
                         JT_A(part_alb)[o] = make_float4(acc[4 * BLOCK], acc[5 * BLOCK], acc[6 * BLOCK], __int_as_float(acc_i[10 * BLOCK]));
                         JT_A(part_nrm)[o] = make_float4(acc[7 * BLOCK], acc[8 * BLOCK], acc[9 * BLOCK], 0.0f);

@@ -178,6 +178,7 @@ extern "C" int jt_create_multi(const jt_scene* scene, const jt_scene_bvh* bvh, c
     for (int d = 0; d < ndevices; d++) {
         m.sub[d]->P.tile_stride = m.tile_split ? ndevices : 1;
         m.sub[d]->P.tile_offset = m.tile_split ? d : 0;
+        m.sub[d]->P.tile_stride_rcp = jtk::tile_stride_rcp(m.sub[d]->P.tile_stride);
         // a device's share leaves the other devices' tiles at zero for the summing reduce
         const int st = m.tile_split ? zero_if_stale(m.sub[d]) : JT_OK;
         if (st != JT_OK) {

@@ -44,6 +44,33 @@ JT_PLAN_HD SlotPixel slot_pixel(int g, int width, int height, int tile_stride, i
     return SlotPixel{i, j, i < width && j < height};
 }
 
+// A lane's work item in the trace kernels: its pixel's image coordinates, (j << 16) | i, so a
+// sample start and an item's store take i, j and the pixel index by shifts, masks and multiply-adds
+// (no division by the runtime tile columns). Width and height stay at or below JT_ITEM_MAX_DIM
+// (jt_create rejects more), so no item equals ITEM_NONE: no pixel.
+#define JT_ITEM_MAX_DIM 32768
+constexpr unsigned ITEM_NONE = 0xffffffffu;
+JT_PLAN_HD unsigned item_encode(int i, int j) { return ((unsigned)j << 16) | (unsigned)i; }
+JT_PLAN_HD int item_i(unsigned item) { return (int)(item & 0xffffu); }
+JT_PLAN_HD int item_j(unsigned item) { return (int)(item >> 16); }
+// 1 / tile_stride as the float the slot rule below multiplies by: computed once on the host
+// (DParams::tile_stride_rcp), the IEEE quotient
+JT_PLAN_HD float tile_stride_rcp(int tile_stride) { return 1.0f / (float)tile_stride; }
+// The launch tile of image tile t of the share, (t - offset) / stride. The quotient is exact in
+// integers; t < 2^20 (jt_create) keeps the float product within 2^-3 of it, so adding a half and
+// truncating gives it. Against the integer division in the kernel: cornellbox +0.5 %, its 1/8 share
+// +0.9 % (two runs each, profiles/r06_ab/slot_float_vs_div_r06d.txt; the division's code raised the
+// kernels' spills from 1-2 to 4-6 VGPRs)
+JT_PLAN_HD int launch_tile(int t, int tile_offset, float stride_rcp) {
+    return (int)((float)(t - tile_offset) * stride_rcp + 0.5f);
+}
+// An item's launch slot, the inverse of slot_pixel: image tile (j >> 3) * tiles_x + (i >> 3), the
+// pixel of the tile (j & 7) * 8 + (i & 7)
+JT_PLAN_HD int item_slot(unsigned item, int tiles_x, int tile_offset, float stride_rcp) {
+    const int i = item_i(item), j = item_j(item);
+    return launch_tile((j >> 3) * tiles_x + (i >> 3), tile_offset, stride_rcp) * 64 + (j & 7) * 8 + (i & 7);
+}
+
 // the launch slots inside the image: every pixel the launch traces (edge tiles are clipped)
 JT_PLAN_HD long long traced_pixels(int width, int height, int stride, int offset) {
     const int tiles = plan_tiles(width, height, stride, offset);

@@ -183,6 +183,7 @@ struct DParams {
     // the 8x8 tiles this launch covers: every tile_stride-th from tile_offset (a multi-device context
     // split by pixel tiles, jt_create_multi; 1 / 0 otherwise: every tile)
     int tile_stride, tile_offset;
+    float tile_stride_rcp;  // 1.0f / (float)tile_stride (jtk::tile_stride_rcp), set wherever tile_stride is
     unsigned long long seed;
 };
 

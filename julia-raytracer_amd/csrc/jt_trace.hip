@@ -194,6 +194,7 @@ int make_params(jt_ctx* c, const jt_scene* scene, const jt_params* params, const
             P.tile_offset = o;
         }
     }
+    P.tile_stride_rcp = tile_stride_rcp(P.tile_stride);
     // sample streams: from the pixels this context traces (a tile share traces 1/stride of them)
     c->lk = stream_log2(((long long)W * H + P.tile_stride - 1) / P.tile_stride, std::max(1, params->batch));
     forced_streams = false;
@@ -224,8 +225,10 @@ int alloc_accumulators(jt_ctx* c, bool forced_streams) {
         return st;
     // persistent scheduling: unit counters (zeroed before each launch)
     c->tiles = ((W + 7) / 8) * ((H + 7) / 8);
-    if (c->tiles >= (1 << 20))  // the per-lane work items address a pixel as tile * 64 + l
+    if (c->tiles >= (1 << 20))  // an item's slot: the float quotient of its tile (item_slot, jt_plan.h)
         return jt::fail(JT_ERR_UNSUPPORTED, "image above 2^20 8x8 tiles (67 Mpixels)");
+    if (W > JT_ITEM_MAX_DIM || H > JT_ITEM_MAX_DIM)  // the per-lane work items hold a pixel as (j << 16) | i
+        return jt::fail(JT_ERR_UNSUPPORTED, "image wider or higher than 32768 pixels");
     if ((st = device_alloc(c, SCHED_BYTES, "schedule", &sched)) != JT_OK) return st;
     // the sample streams' means (k > 1): image, albedo + hits, normal per (stream, slot of the
     // launch's tiles: a tile share holds only its own pixels). Too little memory for k streams
