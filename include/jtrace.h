@@ -28,6 +28,8 @@
  *   jt_eval_hits       ~ eval_shading_position / eval_shading_normal / eval_material (src/scene.jl:416-673)
  *                      at the caller's hit records; jt_camera_rays ~ sample_camera (src/trace.jl:651-674);
  *                      jt_gbuffer the two around jt_intersect: the surface under every pixel
+ *   jt_radiance        ~ trace_sample (src/trace.jl:584-649) without its camera: the integrator's running
+ *                      mean of radiance along the caller's own rays
  *   jt_destroy / jt_last_error — lifetime and error reporting (the reference throws Julia exceptions)
  *
  * Host helpers (run on the CPU, no device needed) that restate the reference's host code
@@ -655,6 +657,48 @@ int jt_eval_hits_device(jt_ctx* ctx, int64_t n, const void* d_rays, const void* 
 int jt_camera_rays_device(jt_ctx* ctx, int32_t sample, void* d_rays);
 int jt_gbuffer_device(jt_ctx* ctx, int32_t sample, void* d_rays /* may be NULL */, void* d_hits /* may be NULL */,
                       void* d_surfaces);
+
+/* ---- radiance along the caller's rays ---------------------------------------------------- */
+/* The path integrator itself (trace_sample, src/trace.jl:584-649: trace_path or trace_naive, the
+ * BSDFs, light sampling and MIS) on rays no camera of the context makes: a light probe, a lightmap
+ * texel, a lat-long panorama, a fisheye or stereo rig, one path re-traced for debugging.
+ * jt_radiance: for every ray i (rays[6 i ..] = origin, direction) the running mean of samples
+ * [sample_begin, sample_end), in order. For sample s:
+ *   - rng = rng_init(params.seed, stream_base + i, s), the stream the integrator gives pixel
+ *     stream_base + i, and the sample prologue's four floats are drawn and discarded (the two
+ *     rand2f a camera ray uses);
+ *   - the path state starts as trace_sample's does, with (o, d) taken from ray i;
+ *   - the context's sampler (trace_path or trace_naive) runs with the context's bounces, nocaustics,
+ *     envhidden and clamp, in the traversal the context was created with;
+ *   - trace_sample's epilogue: non-finite radiance becomes 0, then the clamp; the target is
+ *     (radiance, 1) if a bounce-0 surface was accepted or the ray escaped to a visible environment,
+ *     else (0, 0, 0, 0);
+ *   - acc = acc * (1 - w) + target * w with w = 1 / (float)(c + 1), c = s - sample_begin, acc from 0,
+ *     in float32 without fused multiply-adds, the weight as the integrator computes it.
+ * rgba[4 i ..] = acc after the last sample.
+ * The direction is used as given. The integrator's camera rays have unit length, and a caller's
+ * must too for the BSDF terms to mean anything; it is neither checked nor normalised (normalising
+ * would change the bits of camera rays).
+ * So with rays = jt_camera_rays(ctx, s), n = W*H, stream_base = 0 and the range [s, s + 1) the
+ * result is, bit for bit at every pixel, the image of a context whose first and only traced
+ * sample is s. A ray's result depends on the ray, its stream and the sample range only: an array
+ * split over several calls, stream_base advanced by the rays already done, gives the bits of one call.
+ * The *_device variant takes device pointers on the context's device (d_rgba aligned to 16 bytes),
+ * runs on the context's stream and returns when it is idle. The host variant stages through the
+ * buffers the ray queries' host variants use.
+ * It reads the scene and the parameters only: image, AOVs, stream means, variance, the adaptive
+ * mask and every jt_counters field stay bit for bit as they were, queued samples stay queued.
+ * Errors, in this order: JT_ERR_INVALID (naming the argument) for a NULL ctx, rays or output,
+ * n < 0 or n > 2^30, stream_base < 0 or stream_base + n > 2^31, sample_begin < 0, sample_end <=
+ * sample_begin, more than 2^24 samples, a d_rgba not aligned to 16 bytes, before the context is
+ * looked at and before anything is written; n == 0 returns JT_OK with no device work;
+ * JT_ERR_UNSUPPORTED for a multi-device context; JT_ERR_STATE for a failed context.
+ * Non-finite ray components are the caller's responsibility: every lane ends in a bounded number
+ * of steps for any input, the result for such a ray is unspecified. */
+int jt_radiance(jt_ctx* ctx, int64_t n, const float* rays /* n x (o, d) */, int64_t stream_base,
+                int32_t sample_begin, int32_t sample_end, float* rgba /* n x 4 */);
+int jt_radiance_device(jt_ctx* ctx, int64_t n, const void* d_rays, int64_t stream_base,
+                       int32_t sample_begin, int32_t sample_end, void* d_rgba);
 
 /* zero accumulators (at once if their device pointers were handed out, else before they are
  * next read or overwritten), samples = 0, queued samples dropped */

@@ -1,7 +1,7 @@
 // jt_context.h — the device context behind include/jtrace.h's jt_ctx and the few functions its
 // pieces share: jt_trace.hip (creation, the sample queue, the getters), jt_multi.hip (the
-// multi-device context), jt_denoise.hip, jt_error.hip, jt_adapt.hip, jt_intersect.hip and
-// jt_surface.hip (their context halves). Not part of the ABI.
+// multi-device context), jt_denoise.hip, jt_error.hip, jt_adapt.hip, jt_intersect.hip,
+// jt_surface.hip and jt_radiance.hip (their context halves). Not part of the ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -149,6 +149,10 @@ void query_free(jt_ctx* c);
 int query_setup(jt_ctx* c);
 int query_grow(jt_ctx* c, int which, size_t bytes, const char* what);
 int query_stage(jt_ctx* c, int64_t n);
+// the scene a persistent query grid of `grid` workgroups traverses (query_kernel, and jt_radiance.hip's
+// radiance_kernel): the context's HBM scene with the ring entries in use and, when the scene's stack
+// bound exceeds them (*ovf), an overflow area of the grid's own in q_grow[Q_OVF], grown to fit
+int query_scene(jt_ctx* c, int grid, jtd::DScene* S, bool* ovf);
 
 // xyz of np float4 to np x 3 floats (the AOV getters)
 inline void unpack3(const std::vector<float4>& src, float* dst) {

@@ -383,6 +383,10 @@ __device__ __forceinline__ void aov_update(const Aov& a, v3 ta, v3 tn) {
     p[8 * BLOCK] = p[8 * BLOCK] * omw + tn.y * aw;
     p[9 * BLOCK] = p[9 * BLOCK] * omw + tn.z * aw;
 }
+// the sink of a driver that keeps no AOV means (jt_radiance.hip: a caller's ray has no pixel)
+struct NoAov {};
+template <int F>
+__device__ __forceinline__ void aov_update(const NoAov&, v3, v3) {}
 
 template <int F, class AovT>
 __device__ __forceinline__ bool path_hit(const DScene& S, const DParams& P, Path& st, Hit isec, const AovT& aov,

@@ -181,23 +181,9 @@ int query_run(jt_ctx* c, int64_t n, const void* d_rays, const void* d_inst, void
     int st = query_setup(c);
     if (st != JT_OK) return st;
     const int grid = jtq::query_grid(n, c->cus);
-    DScene S = c->S;
-    // the context's ring entries in use (option test_lds_ring shortens it), within this kernel's ring
-    S.ring = c->S.ring < jtq::QUERY_RING ? c->S.ring : jtq::QUERY_RING;
-    const int need = c->S.stack_need;
-    const bool ovf = need > S.ring;
-    S.ovf = nullptr;
-    S.ovf_stride = 0;
-    if (ovf) {  // an overflow area of this grid's own (the trace kernel's belongs to its grid)
-        const size_t entries = jtq::query_ovf_entries(grid, need);
-        if (entries > c->q_ovf_entries) {
-            c->q_ovf_entries = 0;
-            if ((st = query_grow(c, jt_ctx::Q_OVF, entries * sizeof(int), "query stack overflow")) != JT_OK) return st;
-            c->q_ovf_entries = entries;
-        }
-        S.ovf = (int*)c->q_grow[jt_ctx::Q_OVF];
-        S.ovf_stride = need;
-    }
+    DScene S;
+    bool ovf;
+    if ((st = query_scene(c, grid, &S, &ovf)) != JT_OK) return st;
     jtk::DQuery Q{};
     Q.rays = (const float*)d_rays;
     Q.inst = (const int*)d_inst;
@@ -282,6 +268,28 @@ int jtc::query_setup(jt_ctx* c) {
     c->q_to_dev = (int*)a;
     c->q_to_ref = (int*)b;
     c->q_counter = (unsigned*)w;
+    return JT_OK;
+}
+
+int jtc::query_scene(jt_ctx* c, int grid, DScene* out, bool* ovf) {
+    DScene S = c->S;
+    // the context's ring entries in use (option test_lds_ring shortens it), within this kernel's ring
+    S.ring = c->S.ring < jtq::QUERY_RING ? c->S.ring : jtq::QUERY_RING;
+    const int need = c->S.stack_need;
+    *ovf = need > S.ring;
+    S.ovf = nullptr;
+    S.ovf_stride = 0;
+    if (*ovf) {  // an overflow area of this grid's own (the trace kernel's belongs to its grid)
+        const size_t entries = jtq::query_ovf_entries(grid, need);
+        if (entries > c->q_ovf_entries) {
+            c->q_ovf_entries = 0;
+            if (const int st = query_grow(c, jt_ctx::Q_OVF, entries * sizeof(int), "query stack overflow")) return st;
+            c->q_ovf_entries = entries;
+        }
+        S.ovf = (int*)c->q_grow[jt_ctx::Q_OVF];
+        S.ovf_stride = need;
+    }
+    *out = S;
     return JT_OK;
 }
 

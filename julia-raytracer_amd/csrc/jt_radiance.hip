@@ -1,0 +1,300 @@
+// jt_radiance.hip — the path integrator on the caller's own rays (include/jtrace.h: jt_radiance and
+// its device-pointer variant; DESIGN.md §6g "Radiance along the caller's rays"): the megakernel's
+// integrator (jt_integrator.h: Path, path_hit, naive_hit, light_hit) driven by the ray queries'
+// persistent, refilling grid (jt_intersect.hip) instead of the megakernel's pixel hand-out.
+//
+// The scene is the context's HBM copy (NCACHE) with the general feature mask, no counters, the
+// 16-entry LDS stack ring and, for a scene whose bound exceeds it, the query grid's own HBM overflow
+// area: query_kernel's configuration. A lane takes a ray and keeps it for all its samples: the mean
+// is defined in sample order, so a lane that owns its ray needs no atomics and no second pass. Its
+// running mean, its sample index and the parked path state (Path::pk) live in the lane's LDS slots
+// (jt_radiance.h), the stack ring beside them.
+//
+// Each iteration of a wave runs one step kind, chosen by a lane vote (radiance_step):
+//   a primitive step   prim_step
+//   a node step        node_step_any, RADIANCE_NODE_REPEAT pops for a lane whose next step is a pop again
+//   a shading step     for the lanes whose query is done: rerun_tie (a light query's instance passed
+//                      to it, as the megakernel's shading phase does), then light_hit when the path
+//                      waits on a light query, else path_hit or naive_hit, then query_start of the
+//                      next scene query or of the next light-instance query. A finished path runs
+//                      trace_sample's epilogue into the lane's mean and starts the ray's next
+//                      sample, or writes rgba[ray] and frees the lane.
+// Light queries go through the traversal loop: the megakernel's path without inline light chains,
+// which gives the bits of the inline chain. Every value a path computes depends on its ray, its
+// stream and its sample only, never on the lane that runs it or on when.
+//
+// Termination: every traversal step pops an entry of a finite tree or tests primitives of a leaf's
+// finite cursor; a tie's re-run happens once per query (REF_RERUN); a path has at most
+// params.bounces bounces, each with at most 129 opacity retries and, per light, a chain of fewer
+// than 100 hits over a finite light list; the sample count of a ray is finite and so is the number
+// of rays. Every iteration advances some lane that has a ray (radiance_step), so every lane frees in
+// a bounded number of steps for any input, non-finite rays included; for those the result is
+// unspecified.
+#include <hip/hip_runtime.h>
+
+#include <string>
+
+#include "jt_context.h"
+#include "jt_integrator.h"
+#include "jt_radiance.h"
+
+namespace jtk {
+
+using jtq::QUERY_REFILL_LANES;
+using jtq::QUERY_RING;
+
+struct DRadiance {
+    const float* rays;      // n x (o, d)
+    float4* rgba;           // n means
+    unsigned* counter;      // the next ray to claim (zeroed before the launch)
+    long long stream_base;  // ray i draws from stream stream_base + i
+    int n;
+    int s_begin, s_end;  // the samples of every ray, in order
+    unsigned claim;      // rays a wave claims with one atomic (query_claim_rays)
+};
+
+// trace_sample's prologue (start_path) for ray `ray`: the sample's stream, its four draws, which a
+// camera would have used, and the path state; the ray is the caller's
+template <int F>
+__device__ __forceinline__ void radiance_start(const DParams& P, const DRadiance& Q, int ray, int sample, Path& st) {
+    st.rng = rng_init(P.seed, (int)(Q.stream_base + ray), sample);  // < 2^31: RADIANCE_MAX_STREAM
+    (void)rand2f(st.rng);
+    (void)rand2f(st.rng);
+    const float* const r = Q.rays + (size_t)ray * 6;
+    st.o = V3(r[0], r[1], r[2]);
+    st.d = V3(r[3], r[4], r[5]);
+    st.set_radiance<F>(V3(0, 0, 0));
+    st.set_weight<F>(V3(1, 1, 1));
+    st.set_max_roughness<F>(0.0f);
+    st.ctl = 0u;
+    st.phase = PH_SCENE;
+}
+
+// the instance of the path's pending query: a light's (sample_lights_pdf), or -1 for the scene
+__device__ __forceinline__ int radiance_query_instance(const DScene& S, const Path& st) {
+    return st.phase == PH_LIGHT ? S.lights[st.li].instance : -1;
+}
+
+#if JT_RADIANCE_WAVES > 0
+#define JT_RADIANCE_WAVES_ATTR __attribute__((amdgpu_waves_per_eu(JT_RADIANCE_WAVES, JT_RADIANCE_WAVES)))
+#else
+#define JT_RADIANCE_WAVES_ATTR
+#endif
+
+template <bool WIDE, bool OVF, int SAMPLER>
+__global__ __launch_bounds__(BLOCK) JT_RADIANCE_WAVES_ATTR void radiance_kernel(DScene S, DParams P, DRadiance Q) {
+    constexpr int F = FT_ALL;
+    __shared__ int ring[QUERY_RING * BLOCK];
+    __shared__ float lane_lds[jtr::RADIANCE_SLOTS * BLOCK];
+    // the texel-decode LUTs into LDS (tex_lut, jt_scene_eval.h)
+    for (int k = threadIdx.x; k < 512; k += BLOCK) tex_lut[k] = k < 256 ? S.srgb_lut[k] : S.byte_lut[k - 256];
+    __syncthreads();
+    int* const stack = ring + threadIdx.x;
+    float* const acc = lane_lds + jtr::RADIANCE_ACC * BLOCK + threadIdx.x;
+    int* const cur = reinterpret_cast<int*>(lane_lds + jtr::RADIANCE_SAMPLE * BLOCK + threadIdx.x);
+    const int slot = (int)blockIdx.x * BLOCK + (int)threadIdx.x;  // the lane's HBM stack-overflow area
+    Counters cnt{0, 0, 0, 0};
+    const NoAov aov{};
+    Path st;
+    st.pk = lane_lds + jtr::RADIANCE_PARK * BLOCK + threadIdx.x;
+    st.phase = PH_SCENE;
+    st.li = 0;
+    Trav T;
+    T.sp = 0;
+    T.nprim = 0;
+    T.nxt = W_EMPTY;
+    T.nh = 0;
+    int ray = -1;  // the lane's ray; -1: none
+    bool drained = false;          // every ray is claimed
+    unsigned wnext = 0, wend = 0;  // the wave's reserve of claimed rays [wnext, wend)
+    for (;;) {
+        // ---- refill (query_kernel's): the k-th lane without a ray takes the k-th ray of the wave's reserve
+        const unsigned long long idle = __builtin_amdgcn_ballot_w64(ray < 0);
+        const int nidle = __popcll(idle);
+        if (nidle == 64 && drained) break;
+        if (!drained && nidle >= QUERY_REFILL_LANES) {
+            if (wnext >= wend) {
+                unsigned base = 0;
+                if ((threadIdx.x & 63) == 0) base = atomicAdd(Q.counter, Q.claim);
+                base = __builtin_amdgcn_readfirstlane(base);
+                wnext = base;
+                wend = base + Q.claim < (unsigned)Q.n ? base + Q.claim : (unsigned)Q.n;  // < 2^32: query_counter_bound
+                drained = base >= (unsigned)Q.n;
+            }
+            if (!drained) {
+                const unsigned avail = wend - wnext, take = (unsigned)nidle < avail ? (unsigned)nidle : avail;
+                const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(idle >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)idle, 0u));
+                if (ray < 0 && rank < take) {
+                    ray = (int)(wnext + rank);
+                    acc[0] = 0.0f;
+                    acc[BLOCK] = 0.0f;
+                    acc[2 * BLOCK] = 0.0f;
+                    acc[3 * BLOCK] = 0.0f;
+                    *cur = Q.s_begin;
+                    radiance_start<F>(P, Q, ray, Q.s_begin, st);
+                    query_start<WIDE>(S, T, st.o, st.d, -1, stack);
+                }
+                wnext += take;
+            }
+        }
+        // ---- one step kind for the wave (radiance_step); a lane's own sequence of steps is
+        // unchanged, it only waits while another kind runs
+        const bool wantp = ray >= 0 && T.nprim > 0, wantn = ray >= 0 && wants_node<WIDE>(T);
+        const bool wants = ray >= 0 && query_done<WIDE>(T);
+        const int np = __popcll(__builtin_amdgcn_ballot_w64(wantp)), nn = __popcll(__builtin_amdgcn_ballot_w64(wantn));
+        const int ns = __popcll(__builtin_amdgcn_ballot_w64(wants));
+        const int kind = jtr::radiance_step(np, nn, ns);
+        if (kind == jtr::STEP_PRIM) {
+            if (wantp) prim_step<0, F>(S, T, cnt);
+        } else if (kind == jtr::STEP_NODE) {
+            // RADIANCE_NODE_REPEAT pops per node iteration: a lane whose next step is again a
+            // stack pop takes it at once (the megakernel's JT_NODE_REPEAT: the same steps in the same
+            // per-lane order, fewer votes)
+#pragma unroll
+            for (int k = 0; k < jtr::RADIANCE_NODE_REPEAT; k++)
+                if (ray >= 0 && wants_node<WIDE>(T)) node_step_any<WIDE, QUERY_RING, OVF, 0, true, F>(S, T, stack, slot, cnt);
+        } else if (wants && !rerun_tie<WIDE>(S, T, st.o, st.d, radiance_query_instance(S, st), stack)) {
+            // ---- shading step: the lane consumes its hit and issues its next query
+            bool done;
+            if (SAMPLER == 1 && st.phase == PH_LIGHT) done = light_hit<F>(S, P, st, query_hit(T));
+            else if (SAMPLER == 2) done = naive_hit<F>(S, P, st, query_hit(T), aov, cnt.shades);
+            else done = path_hit<F>(S, P, st, query_hit(T), aov, cnt.shades);
+            if (done) {
+                // trace_sample's epilogue (src/trace.jl:625-648), into the ray's running mean
+                v3 radiance = st.radiance<F>();
+                if (!all_finite(radiance)) radiance = V3(0, 0, 0);
+                const float mr = max3(radiance);
+                if (mr > P.clamp) radiance = radiance * (P.clamp / mr);
+                const int sample = *cur;
+                const float w = jl_rcp_weight((float)(sample - Q.s_begin + 1));
+                const float omw = 1 - w;
+                const bool hit = st.flag(F_HIT);
+                const bool env = !hit && !P.envhidden && S.nenvs != 0;
+                const v4 target = (hit || env) ? V4(radiance.x, radiance.y, radiance.z, 1) : V4(0, 0, 0, 0);
+                acc[0] = acc[0] * omw + target.x * w;
+                acc[BLOCK] = acc[BLOCK] * omw + target.y * w;
+                acc[2 * BLOCK] = acc[2 * BLOCK] * omw + target.z * w;
+                acc[3 * BLOCK] = acc[3 * BLOCK] * omw + target.w * w;
+                if (sample + 1 >= Q.s_end) {
+                    Q.rgba[ray] = make_float4(acc[0], acc[BLOCK], acc[2 * BLOCK], acc[3 * BLOCK]);
+                    ray = -1;
+                } else {
+                    *cur = sample + 1;
+                    radiance_start<F>(P, Q, ray, sample + 1, st);
+                }
+            }
+            if (ray >= 0) query_start<WIDE>(S, T, st.o, st.d, radiance_query_instance(S, st), stack);
+        }
+    }
+}
+
+}  // namespace jtk
+
+// ---- the context's half (jt_context.h)
+using namespace jtc;
+using jtd::DScene;
+
+namespace {
+
+constexpr int BLOCK = jtk::BLOCK;
+
+template <bool WIDE, bool OVF, int SAMPLER>
+void launch_radiance(int grid, hipStream_t stream, const DScene& S, const jtd::DParams& P, const jtk::DRadiance& Q) {
+    hipLaunchKernelGGL((jtk::radiance_kernel<WIDE, OVF, SAMPLER>), dim3((unsigned)grid), dim3(BLOCK), 0, stream, S, P, Q);
+}
+
+// the checks both entry points share, in the header's order; *done: n == 0, nothing to do
+int radiance_check(const jt_ctx* c, int64_t n, const void* rays, const char* rays_name, int64_t stream_base, int32_t s0,
+                   int32_t s1, const void* out, const char* out_name, bool device, bool* done) {
+    *done = false;
+    if (!c) return jt::fail(JT_ERR_INVALID, "ctx is NULL");
+    if (!rays) return jt::fail(JT_ERR_INVALID, std::string(rays_name) + " is NULL");
+    if (!out) return jt::fail(JT_ERR_INVALID, std::string(out_name) + " is NULL");
+    if (const char* const msg = jtr::radiance_range_error(n, stream_base, s0, s1)) return jt::fail(JT_ERR_INVALID, msg);
+    if (device && ((uintptr_t)out & 15)) return jt::fail(JT_ERR_INVALID, std::string(out_name) + " must be aligned to 16 bytes");
+    if (n == 0) {
+        *done = true;
+        return JT_OK;
+    }
+    if (c->multi)
+        return jt::fail(JT_ERR_UNSUPPORTED,
+                        "jt_radiance is not available on a multi-device context (jt_create_multi): use one context per device");
+    if (c->failed) return jt::fail(JT_ERR_STATE, "a previous launch failed; jt_reset the context");
+    return JT_OK;
+}
+
+// n >= 1 rays from device pointers, on the context's stream; returns once the stream is idle
+int radiance_run(jt_ctx* c, int64_t n, const void* d_rays, int64_t stream_base, int32_t s0, int32_t s1, void* d_rgba) {
+    (void)hipSetDevice(c->device);
+    int st = query_setup(c);
+    if (st != JT_OK) return st;
+    const int grid = jtq::query_grid(n, c->cus);
+    DScene S;
+    bool ovf;
+    if ((st = query_scene(c, grid, &S, &ovf)) != JT_OK) return st;
+    jtk::DRadiance Q{};
+    Q.rays = (const float*)d_rays;
+    Q.rgba = (float4*)d_rgba;
+    Q.counter = c->q_counter;
+    Q.stream_base = (long long)stream_base;
+    Q.n = (int)n;
+    Q.s_begin = s0;
+    Q.s_end = s1;
+    Q.claim = (unsigned)jtq::query_claim_rays(n, grid);
+    hipError_t e = hipMemsetAsync(c->q_counter, 0, sizeof(unsigned), c->stream);
+    if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync radiance ray counter");
+    const int form = (c->choice.wide ? 4 : 0) | (ovf ? 2 : 0) | (c->sampler == 2 ? 1 : 0);
+    switch (form) {
+        case 0: launch_radiance<false, false, 1>(grid, c->stream, S, c->P, Q); break;
+        case 1: launch_radiance<false, false, 2>(grid, c->stream, S, c->P, Q); break;
+        case 2: launch_radiance<false, true, 1>(grid, c->stream, S, c->P, Q); break;
+        case 3: launch_radiance<false, true, 2>(grid, c->stream, S, c->P, Q); break;
+        case 4: launch_radiance<true, false, 1>(grid, c->stream, S, c->P, Q); break;
+        case 5: launch_radiance<true, false, 2>(grid, c->stream, S, c->P, Q); break;
+        case 6: launch_radiance<true, true, 1>(grid, c->stream, S, c->P, Q); break;
+        default: launch_radiance<true, true, 2>(grid, c->stream, S, c->P, Q); break;
+    }
+    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "radiance kernel launch");
+    if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) {
+        c->failed = true;
+        return hip_fail(e, "radiance kernel");
+    }
+    return JT_OK;
+}
+
+}  // namespace
+
+static_assert(jtr::RADIANCE_LDS_BYTES <= 64 * 1024, "radiance_kernel's static LDS");
+static_assert(sizeof(jt_hit) >= 4 * sizeof(float), "the host variant stages a ray's mean in its jt_hit slot of Q_OUT");
+
+extern "C" {
+
+int jt_radiance_device(jt_ctx* c, int64_t n, const void* d_rays, int64_t stream_base, int32_t sample_begin, int32_t sample_end,
+                       void* d_rgba) {
+    bool done;
+    if (const int st = radiance_check(c, n, d_rays, "d_rays", stream_base, sample_begin, sample_end, d_rgba, "d_rgba", true, &done))
+        return st;
+    return done ? JT_OK : radiance_run(c, n, d_rays, stream_base, sample_begin, sample_end, d_rgba);
+}
+
+int jt_radiance(jt_ctx* c, int64_t n, const float* rays, int64_t stream_base, int32_t sample_begin, int32_t sample_end,
+                float* rgba) {
+    bool done;
+    if (const int st = radiance_check(c, n, rays, "rays", stream_base, sample_begin, sample_end, rgba, "rgba", false, &done)) return st;
+    if (done) return JT_OK;
+    (void)hipSetDevice(c->device);
+    const size_t N = (size_t)n;
+    // Q_OUT holds a jt_hit (24 bytes) per staged ray: room for a ray's 16-byte mean
+    if (const int st = query_stage(c, n)) return st;
+    void* const d_rays = c->q_grow[jt_ctx::Q_RAYS];
+    void* const d_out = c->q_grow[jt_ctx::Q_OUT];
+    hipError_t e;
+    if ((e = hipMemcpy(d_rays, rays, N * 6 * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess)
+        return hip_fail(e, "hipMemcpy radiance rays");
+    if (const int st = radiance_run(c, n, d_rays, stream_base, sample_begin, sample_end, d_out)) return st;
+    if ((e = hipMemcpy(rgba, d_out, N * 4 * sizeof(float), hipMemcpyDeviceToHost)) != hipSuccess)
+        return hip_fail(e, "hipMemcpy radiance results");
+    return JT_OK;
+}
+
+}  // extern "C"

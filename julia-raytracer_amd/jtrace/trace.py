@@ -347,6 +347,26 @@ class TraceState:
                                                 surf.ctypes.data_as(C.POINTER(abi.jt_surface))))
         return rays, hits, surf
 
+    # --- radiance along the caller's rays (jt_radiance: include/jtrace.h)
+    def radiance(self, rays, sample_begin: int = 0, sample_end: int = 1, stream_base: int = 0):
+        """jt_radiance: the integrator's running mean of samples [sample_begin, sample_end) along
+        every ray (n, 6) = (origin, unit direction), ray i drawing from the random stream of pixel
+        stream_base + i: (n, 4) float32 rgba. A numpy array gives a numpy array; a torch tensor on
+        the context's device goes zero-copy through jt_radiance_device and gives a tensor there.
+        With camera_rays(s), the range [s, s + 1) and stream_base 0 it is the image of a context
+        whose only sample is s, bit for bit. The context's image and counters are untouched."""
+        if hasattr(rays, "data_ptr"):
+            torch, n = self._device_rays(rays)
+            out = torch.empty((n, 4), dtype=torch.float32, device=rays.device)
+            abi.check(self.lib, self.lib.jt_radiance_device(self.handle, n, rays.data_ptr(), int(stream_base),
+                                                            int(sample_begin), int(sample_end), out.data_ptr()))
+            return out
+        rays = _host_rays(rays)
+        out = np.empty((len(rays), 4), np.float32)
+        abi.check(self.lib, self.lib.jt_radiance(self.handle, len(rays), rays.ctypes.data_as(abi.f32p), int(stream_base),
+                                                 int(sample_begin), int(sample_end), out.ctypes.data_as(abi.f32p)))
+        return out
+
     def counters(self) -> dict:
         c = abi.jt_counters()
         abi.check(self.lib, self.lib.jt_get_counters(self.handle, C.byref(c)))
