@@ -738,14 +738,34 @@ __device__ __forceinline__ DScene blob_scene(const DScene& S, const uint4* blob)
 // touched. The nodes are the blob's first array, the wide records follow (JT_SCENE_ARRAYS): their
 // count is the gap, two 16-B units per node (an empty array keeps one unit: no node). The TLAS
 // nodes come first (layout_scene), so the index gives the level.
+// Instance roots (JT_INST_ROOTS, jt_push.h): a TLAS leaf's baked entries name root rows, and the same
+// pass writes the rows: row i, node iroot0 + i of the LDS node array, is the baked BLAS root of
+// instance i, over the LDS copy of inst_trav (4 units per instance up to inst_blas; an empty array
+// keeps one unit: no row). A row's sources are the blob in HBM, which nobody writes, so a row never
+// sees another thread's half-baked node; its destination is read by nothing before the barrier.
+// (That is one instance record and one root node re-read from HBM per instance, per workgroup and
+// launch: a few loads from L2 against a persistent launch of tens of milliseconds.)
 __device__ __forceinline__ void bake_nodes(const DScene& S, uint4* blob) {
     uint4* const nodes = blob + S.o_nodes;
     const int nnodes = (S.o_wnodes - S.o_nodes) >> 1;
+    const int iroot0 = JT_INST_ROOTS ? instance_root_base(S.o_nodes, S.o_inst_trav) : 0;
     for (int k = threadIdx.x; k < nnodes; k += BLOCK) {
         uint4& b = nodes[2 * k + 1];  // DNode::b: z the start word, w the meta word
-        const BakedNode bn = bake_node(b.w, (int)b.z, k < S.tlas_nnodes ? T_TLAS : T_BLAS);
+        const BakedNode bn = bake_node(b.w, (int)b.z, k < S.tlas_nnodes ? T_TLAS : T_BLAS, iroot0);
         b.z = bn.e0;
         b.w = bn.meta;
+    }
+    if (JT_INST_ROOTS) {
+        const int ninst = (S.o_inst_blas - S.o_inst_trav) >> 2;
+        for (int i = threadIdx.x; i < ninst; i += BLOCK) {
+            const uint4* const root = S.blob + S.o_nodes + 2 * (int)S.blob[S.o_inst_blas + i].x;
+            uint4 b = root[1];
+            const BakedNode bn = bake_node(b.w, (int)b.z, T_BLAS);
+            b.z = bn.e0;
+            b.w = bn.meta;
+            nodes[2 * (iroot0 + i)] = root[0];
+            nodes[2 * (iroot0 + i) + 1] = b;
+        }
     }
 }
 

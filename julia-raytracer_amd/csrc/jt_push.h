@@ -85,10 +85,13 @@ constexpr unsigned BAKE_LEAF = 1u << 27;
 struct BakedNode {
     unsigned e0, meta;  // the node's words z and w
 };
-JT_PUSH_HD BakedNode bake_node(unsigned meta, int start, unsigned level) {
+// iroot0 (instance roots, below): added to a TLAS leaf's start, whose run of instance entries then
+// names the instances' root rows; the run stays affine in the slot number
+JT_PUSH_HD BakedNode bake_node(unsigned meta, int start, unsigned level, int iroot0 = 0) {
     const bool internal = (meta >> 24) != 0;
     const bool blas = level != 0u;  // T_BLAS, against T_TLAS = 0
     const unsigned num = meta & 0xffffu;
+    if (!internal && !blas) start += iroot0;
     const unsigned tag = (internal ? level << 30 : PUSH_T_INST << 30) | PUSH_SNAP_NONE;
     // (a TLAS leaf holds at most PUSH_SLOTS instances: the host layout rejects larger ones)
     const unsigned npush = internal ? 2u : blas ? 0u : (num < (unsigned)PUSH_SLOTS ? num : (unsigned)PUSH_SLOTS);
@@ -128,5 +131,23 @@ JT_PUSH_HD PushPlan push_plan_baked(unsigned e0, unsigned meta, int negmask, int
     }
     return p;
 }
+
+// Instance roots (JT_INST_ROOTS, jt_traverse.h). The baking kernels read one word of an instance's
+// record while they traverse, the index of its BLAS root node, and that node is a constant of the
+// scene. So the bake pass also writes, for every instance i, a baked copy of its root node, and an
+// instance's stack entry carries the copy's node index: a pop reads its node at the entry's index
+// whatever the entry's type, without reading the instance record first.
+// The copies live in the LDS copy of the blob's inst_trav array (64 B per instance, read only with
+// instance transforms, which no baking kernel has): copy i is node iroot0 + i, counted in 32-B nodes
+// from the node array's base. o_nodes and o_inst_trav are the arrays' blob offsets in 16-B units;
+// iroot0 is the first whole node at or after inst_trav's first byte. The last copy ends at most
+// 16 + 32 n bytes into the n instances' 64 n: tests/instance_root_check.cpp enumerates it.
+JT_PUSH_HD int instance_root_base(int o_nodes, int o_inst_trav) { return (o_inst_trav - o_nodes + 1) >> 1; }
+constexpr unsigned PUSH_IDX_MASK = (1u << 24) - 1;  // IDX_MASK (jt_select.h)
+// the stack entry of instance inst in a baking kernel, and the instance of such an entry
+JT_PUSH_HD unsigned instance_root_entry(int iroot0, int inst) {
+    return PUSH_T_INST << 30 | PUSH_SNAP_NONE | (unsigned)(iroot0 + inst);
+}
+JT_PUSH_HD int instance_of_entry(int iroot0, unsigned e) { return (int)(e & PUSH_IDX_MASK) - iroot0; }
 
 }  // namespace jtk

@@ -99,6 +99,21 @@ __host__ __device__ constexpr bool node_baked() {
     return JT_NODE_BAKE && !OVF && !NCACHE && !WIDE && ft_none(F);
 }
 __host__ __device__ constexpr int push_bit(bool baked) { return baked ? BAKE_MASK_BIT : 0; }
+// Instance roots (jt_push.h): the bake pass also writes a baked copy of every instance's BLAS root
+// node into the LDS copy of inst_trav, and an instance's stack entry in a baking kernel is the
+// copy's node index, so node_step reads its node at the popped index for every entry type and has
+// no instance arm; inst_leaf_query reads the copy too. The baking kernels have neither FT_XFORM nor
+// FT_QUAD, so an instance visit is only "the current instance is this one", a select.
+// 0: instance entries carry the instance number and the step reads S.inst_blas first (A/B runs).
+#ifndef JT_INST_ROOTS
+#define JT_INST_ROOTS 1
+#endif
+// the node index of instance 0's root row in a kernel whose push bit is pb: wave-uniform, from two
+// of the scene's blob offsets; 0 in every kernel that does not bake (pb 0), whose entries keep the
+// instance number
+__device__ __forceinline__ int inst_root_base(const DScene& S, int pb) {
+    return JT_INST_ROOTS && pb ? instance_root_base(S.o_nodes, S.o_inst_trav) : 0;
+}
 
 __device__ __forceinline__ int neg_mask(v3 d, int flip) {
     return ((d.x < 0 ? 1 : 0) | (d.y < 0 ? 2 : 0) | (d.z < 0 ? 4 : 0)) ^ flip;
@@ -182,10 +197,12 @@ __device__ __forceinline__ void query_begin_wide(const DScene& S, Trav& T, v3 o,
 constexpr unsigned WROOT_SCENE = 0u;  // the TLAS root record
 __device__ __forceinline__ unsigned wroot_instance(int inst) { return W_LEAF | W_INST | (unsigned)inst; }
 // query_begin for either traversal: a closest-hit scene query, or (inst >= 0) the
-// intersect_instance_bvh of sample_lights_pdf
+// intersect_instance_bvh of sample_lights_pdf. In a baking kernel (pb set) the instance's entry
+// carries its root row (instance_root_entry, jt_push.h: the instance number plus iroot0)
 template <bool WIDE>
 __device__ __forceinline__ void query_start(const DScene& S, Trav& T, v3 o, v3 d, int inst, int* stack, int rerun = 0,
                                             int pb = 0) {
+    if (JT_INST_ROOTS && pb && inst >= 0) inst += inst_root_base(S, pb);
     if (WIDE) query_begin_wide(S, T, o, d, inst < 0 ? WROOT_SCENE : wroot_instance(inst), rerun);
     else query_begin(S, T, o, d, inst < 0 ? ((T_TLAS << 30) | SNAP_NONE) : ((T_INST << 30) | SNAP_NONE | (unsigned)inst), stack, rerun, pb);
 }
@@ -355,7 +372,12 @@ __device__ __forceinline__ void node_step(const DScene& S, Trav& T, int* stack, 
     constexpr int PB = push_bit(BAKED);
     const unsigned e = st_pop<RING, OVF>(S, T, stack, pixel);
     unsigned type = e >> 30, idx = e & IDX_MASK;
-    if (type == T_INST) {  // instance visit: inverse(frame, true) precomputed (src/bvh.jl:345,502)
+    if constexpr (BAKED && JT_INST_ROOTS) {
+        // an instance entry is the node index of the instance's root row (jt_push.h): idx is the
+        // node to read whatever the type, and the visit is a select
+        if (COUNT) cnt.instances += type == T_INST ? 1u : 0u;
+        T.cur_inst = type == T_INST ? instance_of_entry(inst_root_base(S, PB), e) : T.cur_inst;
+    } else if (type == T_INST) {  // instance visit: inverse(frame, true) precomputed (src/bvh.jl:345,502)
         if (COUNT) cnt.instances++;
         const int4 ib = S.inst_blas[idx];  // blas_root, identity, kind, shape | leaf root (one load: x, y adjacent)
         enter_instance<XF>(S, T, idx, ib, PB);
@@ -386,7 +408,8 @@ __device__ __forceinline__ void node_step(const DScene& S, Trav& T, int* stack, 
         DNode nd = S.nodes[idx];
         // JT_NODE_READ16 (baking kernels): the node as two 16-B reads issued together, as the
         // NCACHE arm pins its nb, instead of 16 + 8 B and a dependent 8-B read of start/meta
-        // behind the box test. Not adopted: EXPERIMENTS.md.
+        // behind the box test. Measured again on the step without an instance arm, per kernel
+        // family, and not adopted: EXPERIMENTS.md ("Instance-root rows").
         if (JT_NODE_READ16 && BAKED) __asm__("" : "+v"(nd.b.x), "+v"(nd.b.y), "+v"(nd.b.z), "+v"(nd.b.w));
         if (!intersect_bbox(T.lo, T.ldinv, ray_eps, T.tmax, nd.a, nd.b)) return;
         nb = nd.b;
@@ -595,12 +618,21 @@ __device__ __forceinline__ void inst_leaf_query(const DScene& S, Trav& T, v3 o, 
     T.low = 0;
     T.nxt = W_EMPTY;
     if (COUNT) cnt.instances++;
-    const int4 ib = S.inst_blas[inst];
-    // the query has just started in world space (inst_space 0), so enter_instance's return to the
-    // world ray is dead here; this overwrites query_reset's cur_inst and cur_kind
-    enter_instance<XF>(S, T, (unsigned)inst, ib, PB);
+    int root;
+    if constexpr (JT_INST_ROOTS && PB != 0) {
+        // the instance's root row (jt_push.h): no instance record is read. A one-leaf root's baked
+        // words are its own: start, and the count in meta's low 16 bits
+        T.cur_inst = inst;
+        root = inst_root_base(S, PB) + inst;
+    } else {
+        const int4 ib = S.inst_blas[inst];
+        // the query has just started in world space (inst_space 0), so enter_instance's return to the
+        // world ray is dead here; this overwrites query_reset's cur_inst and cur_kind
+        enter_instance<XF>(S, T, (unsigned)inst, ib, PB);
+        root = ib.x;
+    }
     if (COUNT) cnt.nodes++;
-    const DNode nd = S.nodes[ib.x];
+    const DNode nd = S.nodes[root];
     const bool pass = intersect_bbox(T.lo, T.ldinv, ray_eps, T.tmax, nd.a, nd.b);
     T.prim = pass ? __float_as_int(nd.b.z) : 0;
     T.nprim = pass ? (int)(__float_as_uint(nd.b.w) & 0xffffu) : 0;
