@@ -6,6 +6,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <initializer_list>
+#include <type_traits>
 #include <vector>
 
 #include "jt_internal.h"
@@ -102,7 +104,9 @@ struct jt_ctx {
     // ints) and the host variants' staging of rays, instance ids and results (q_stage_rays
     // rays) — kept across jt_reset, freed by jt_destroy (query_free). The surface calls
     // (jt_eval_hits, jt_camera_rays, jt_gbuffer; jt_surface.hip) stage rays and hits in the same
-    // buffers and their jt_surface records in Q_SURF (q_stage_surf records)
+    // buffers and their jt_surface records in Q_SURF (q_stage_surf records); jt_radiance
+    // (jt_radiance.hip) launches on the same counter and overflow area and stages its rays in
+    // Q_RAYS and its means in Q_OUT
     std::vector<int> inst_new;
     int* q_to_dev = nullptr;
     int* q_to_ref = nullptr;
@@ -142,7 +146,7 @@ int trace_finish(jt_ctx* c, float* ms);
 int flush(jt_ctx* c);
 // frees the ray queries' growing buffers (jt_ctx::q_grow; jt_intersect.hip), for jt_destroy
 void query_free(jt_ctx* c);
-// the ray queries' pieces the surface calls share (jt_intersect.hip). query_setup: the first call's
+// the ray queries' pieces the surface calls and jt_radiance share (jt_intersect.hip). query_setup: the first call's
 // uploads (q_to_dev, q_to_ref, q_counter). query_grow: buffer `which` of q_grow replaced by one of
 // at least `bytes` (its content is not kept); JT_ERR_NOMEM "hipMalloc <what>". query_stage: the
 // staging of rays, instance ids and jt_hit records grown to hold n rays
@@ -153,6 +157,33 @@ int query_stage(jt_ctx* c, int64_t n);
 // radiance_kernel): the context's HBM scene with the ring entries in use and, when the scene's stack
 // bound exceeds them (*ovf), an overflow area of the grid's own in q_grow[Q_OVF], grown to fit
 int query_scene(jt_ctx* c, int grid, jtd::DScene* S, bool* ovf);
+
+// ---- what the calls on the caller's own records share (jt_intersect, jt_occluded; jt_eval_hits,
+// jt_camera_rays, jt_gbuffer; jt_radiance; defined in jt_intersect.hip)
+// The argument checks, in the order include/jtrace.h documents: ctx NULL, each of `args` NULL
+// ("<name> is NULL"), range_error and misaligned (the message of an argument out of range, of a
+// device variant's misaligned pointer; nullptr: none), `empty` (n == 0: *done = true, JT_OK), a
+// multi-device context (JT_ERR_UNSUPPORTED multi_error), a previous launch failed. A call without n
+// passes neither empty nor done.
+struct NamedArg {
+    const void* p;
+    const char* name;
+};
+int ray_call_check(const jt_ctx* c, std::initializer_list<NamedArg> args, const char* range_error, const char* misaligned,
+                   const char* multi_error, bool empty = false, bool* done = nullptr);
+// after a kernel launch on the context's stream: the launch's error ("<what> launch"), then the
+// stream's once it is idle ("<what>"), which marks the context failed
+int launch_finish(jt_ctx* c, const char* what);
+// a blocking hipMemcpy to and from the device; `what` names it in the error
+int copy_in(void* dst, const void* src, size_t bytes, const char* what);
+int copy_out(void* dst, const void* src, size_t bytes, const char* what);
+// f(A, B, C) with a, b, c as std::true_type / std::false_type: three runtime booleans to template
+// arguments (kernel<A(), B(), C()>)
+template <class F>
+void with_bools(bool a, bool b, bool c, F&& f) {
+    const auto pick = [](bool v, auto&& g) { !v ? g(std::false_type{}) : g(std::true_type{}); };
+    pick(a, [&](auto A) { pick(b, [&](auto B) { pick(c, [&](auto C) { f(A, B, C); }); }); });
+}
 
 // xyz of np float4 to np x 3 floats (the AOV getters)
 inline void unpack3(const std::vector<float4>& src, float* dst) {

@@ -1,7 +1,8 @@
 // jt_intersect.h — the integer rules of a ray queries' launch (include/jtrace.h: jt_intersect,
 // jt_occluded; the kernel and the context's half are in jt_intersect.hip): the persistent grid for n
-// rays, the size of its stack overflow area, the growth of the host variants' staging buffers.
-// Plain C++ (no HIP runtime), shared by jt_intersect.hip and the host check (tests/query_plan_check.cpp).
+// rays, the size of its stack overflow area, a wave's reserve of claimed rays (the refill of
+// jt_feed.h runs it), the growth of the host variants' staging buffers.
+// Plain C++ (no HIP runtime), shared by the kernels and the host check (tests/query_plan_check.cpp).
 // Not part of the ABI.
 #pragma once
 
@@ -51,6 +52,29 @@ inline int query_claim_rays(int64_t n, int grid) {
 // more claim per wave of the grid (< 2^32: the counter is 32 bits).
 inline uint64_t query_counter_bound(int64_t n, int grid) {
     return (uint64_t)n + (uint64_t)QUERY_CLAIM_MAX * ((uint64_t)grid * (jtk::BLOCK / 64) + 1);
+}
+
+// A wave's reserve of claimed rays [next, end), and what the refill does to it (feed_refill,
+// jt_feed.h; replayed on the host by tests/query_plan_check.cpp). constexpr: device code runs the
+// members too.
+struct WaveReserve {
+    unsigned next = 0, end = 0;
+    bool drained = false;  // every ray of the launch is claimed: the wave claims no more
+    constexpr bool empty() const { return next >= end; }
+    // the wave's atomicAdd of `claim` on the ray counter of a launch of n rays returned `base`
+    constexpr void claimed(unsigned base, unsigned claim, unsigned n) {
+        next = base;
+        end = base + claim < n ? base + claim : n;  // < 2^32: query_counter_bound
+        drained = base >= n;
+    }
+    // rays that nidle idle lanes take; the k-th of them takes ray next + k, then next += take
+    constexpr unsigned take(unsigned nidle) const { return nidle < end - next ? nidle : end - next; }
+};
+
+// n of a call outside 0 .. QUERY_MAX_RAYS: the message (`most`: the family's words for the upper
+// bound), else nullptr
+constexpr const char* query_count_error(int64_t n, const char* most) {
+    return n < 0 ? "n must be at least 0" : n > QUERY_MAX_RAYS ? most : nullptr;
 }
 
 // Rays the staging buffers hold after a call of n rays when they held `have`: unchanged while n

@@ -1,6 +1,8 @@
 // jt_intersect.hip — ray queries on a context's scene (include/jtrace.h: jt_intersect, jt_occluded and
 // their device-pointer variants; DESIGN.md §6e "Ray queries"): the megakernel's own traversal
-// (jt_traverse.h) over the caller's rays.
+// (jt_traverse.h) over the caller's rays. The context's half below also holds what every call on
+// the caller's own records shares (jt_context.h; jt_surface.hip and jt_radiance.hip use it): the
+// argument checks, the launch tail, the staging copies, the first call's uploads and the grid's scene.
 //
 // The scene is the context's HBM copy — every array of JT_SCENE_ARRAYS is uploaded in both scene
 // modes, so an LDS-mode context queries through HBM pointers too (NCACHE) — with the general feature
@@ -15,8 +17,9 @@
 // Work distribution: query lengths diverge by orders of magnitude (a miss from outside costs one
 // box test, a ray through a deep scene hundreds of nodes), so the grid is persistent — at most
 // QUERY_WG_PER_CU workgroups per compute unit (jt_intersect.h) — and a wave refills its finished lanes
-// once QUERY_REFILL_LANES of them have no ray: a ballot of those lanes, and the k-th of them takes
-// the k-th ray of the wave's reserve (the megakernel's hand-out, jt_kernels.h). The reserve is
+// once QUERY_REFILL_LANES of them have no ray (feed_refill, jt_feed.h, which radiance_kernel runs
+// too): a ballot of those lanes, and the k-th of them takes the k-th ray of the wave's reserve (the
+// megakernel's hand-out pattern, jt_kernels.h). The reserve (jtq::WaveReserve, jt_intersect.h) is
 // query_claim_rays consecutive rays (64 to 256), claimed by the wave's first lane with one atomicAdd on the
 // launch's ray counter: a claim per refill (a fifth of a million same-address atomics for 2^22
 // rays) bound the whole launch to 2.4 ms whatever the scene (EXPERIMENTS.md). Each iteration then
@@ -28,12 +31,11 @@
 #include <vector>
 
 #include "jt_context.h"
-#include "jt_intersect.h"
+#include "jt_feed.h"
 #include "jt_traverse.h"
 
 namespace jtk {
 
-using jtq::QUERY_REFILL_LANES;
 using jtq::QUERY_VOTE_P;
 using jtq::QUERY_RING;
 
@@ -42,11 +44,10 @@ struct DQuery {
     const int* inst;       // nullptr, or per ray -1 / an instance id in the caller's numbering
     int* hits;             // closest hit: n jt_hit records as 6 words each
     unsigned char* occ;    // any hit: n flags
-    unsigned* counter;     // the next ray to claim (zeroed before the launch)
     const int* to_dev;     // the caller's instance id -> the device's (TLAS leaf order)
     const int* to_ref;     // and back
-    int n, ninst;
-    unsigned claim;        // rays a wave claims with one atomic (query_claim_rays)
+    int ninst;
+    DFeed feed;            // the n rays' hand-out
 };
 
 constexpr int Q_BAD_INSTANCE = -2;
@@ -91,30 +92,11 @@ __global__ __launch_bounds__(BLOCK) void query_kernel(DScene S, DQuery Q) {
     Counters cnt{0, 0, 0, 0};
     Trav T;
     int ray = -1;  // the lane's ray; -1: none
-    bool drained = false;          // every ray is claimed
-    unsigned wnext = 0, wend = 0;  // the wave's reserve of claimed rays [wnext, wend)
-    for (;;) {
-        // ---- refill (wave-uniform control): the k-th lane without a ray takes the k-th ray of the
-        // wave's reserve
-        const unsigned long long idle = __builtin_amdgcn_ballot_w64(ray < 0);
-        const int nidle = __popcll(idle);
-        if (nidle == 64 && drained) break;
-        if (!drained && nidle >= QUERY_REFILL_LANES) {
-            if (wnext >= wend) {  // the wave's reserve is empty: claim Q.claim consecutive rays
-                unsigned base = 0;
-                if ((threadIdx.x & 63) == 0) base = atomicAdd(Q.counter, Q.claim);
-                base = __builtin_amdgcn_readfirstlane(base);
-                wnext = base;
-                wend = base + Q.claim < (unsigned)Q.n ? base + Q.claim : (unsigned)Q.n;  // < 2^32: query_counter_bound
-                drained = base >= (unsigned)Q.n;
-            }
-            if (!drained) {
-                const unsigned avail = wend - wnext, take = (unsigned)nidle < avail ? (unsigned)nidle : avail;
-                const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(idle >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)idle, 0u));
-                if (ray < 0 && rank < take && query_take<WIDE, ANY>(S, Q, T, (int)(wnext + rank), stack)) ray = (int)(wnext + rank);
-                wnext += take;
-            }
-        }
+    jtq::WaveReserve reserve;
+    // ---- refill (jt_feed.h): a lane without a ray takes one of the wave's reserve
+    while (feed_refill(Q.feed, reserve, ray >= 0, [&](int r) {
+        if (query_take<WIDE, ANY>(S, Q, T, r, stack)) ray = r;
+    })) {
         // ---- one step of every lane with a query in flight: one step kind per iteration, by a
         // biased lane vote (the megakernel's, jt_kernels.h), so the SIMD runs one code path; a lane's
         // own sequence of steps is unchanged, it only waits while the other kind runs
@@ -150,29 +132,12 @@ namespace {
 
 constexpr int BLOCK = jtk::BLOCK;
 
-template <bool WIDE, bool OVF, bool ANY>
-void launch_query(int grid, hipStream_t stream, const DScene& S, const jtk::DQuery& Q) {
-    hipLaunchKernelGGL((jtk::query_kernel<WIDE, OVF, ANY>), dim3((unsigned)grid), dim3(BLOCK), 0, stream, S, Q);
-}
-
-// the checks every entry point shares, in the header's order; *done: n == 0, nothing to do
+// the checks every entry point shares; *done: n == 0, nothing to do
 int query_check(const jt_ctx* c, int64_t n, const void* rays, const char* rays_name, const void* out, const char* out_name,
                 bool* done) {
-    *done = false;
-    if (!c) return jt::fail(JT_ERR_INVALID, "ctx is NULL");
-    if (!rays) return jt::fail(JT_ERR_INVALID, std::string(rays_name) + " is NULL");
-    if (!out) return jt::fail(JT_ERR_INVALID, std::string(out_name) + " is NULL");
-    if (n < 0) return jt::fail(JT_ERR_INVALID, "n must be at least 0");
-    if (n > jtq::QUERY_MAX_RAYS) return jt::fail(JT_ERR_INVALID, "n must be at most 2^30 rays");
-    if (n == 0) {
-        *done = true;
-        return JT_OK;
-    }
-    if (c->multi)
-        return jt::fail(JT_ERR_UNSUPPORTED,
-                        "ray queries are not available on a multi-device context (jt_create_multi): query one context per device");
-    if (c->failed) return jt::fail(JT_ERR_STATE, "a previous launch failed; jt_reset the context");
-    return JT_OK;
+    return ray_call_check(c, {{rays, rays_name}, {out, out_name}}, jtq::query_count_error(n, "n must be at most 2^30 rays"), nullptr,
+                          "ray queries are not available on a multi-device context (jt_create_multi): query one context per device",
+                          n == 0, done);
 }
 
 // n >= 1 rays from device pointers, on the context's stream; returns once the stream is idle
@@ -189,31 +154,16 @@ int query_run(jt_ctx* c, int64_t n, const void* d_rays, const void* d_inst, void
     Q.inst = (const int*)d_inst;
     Q.hits = any ? nullptr : (int*)d_out;
     Q.occ = any ? (unsigned char*)d_out : nullptr;
-    Q.counter = c->q_counter;
     Q.to_dev = c->q_to_dev;
     Q.to_ref = c->q_to_ref;
-    Q.n = (int)n;
     Q.ninst = (int)c->inst_new.size();
-    Q.claim = (unsigned)jtq::query_claim_rays(n, grid);
-    hipError_t e = hipMemsetAsync(c->q_counter, 0, sizeof(unsigned), c->stream);
+    Q.feed = {c->q_counter, (int)n, (unsigned)jtq::query_claim_rays(n, grid)};
+    const hipError_t e = hipMemsetAsync(c->q_counter, 0, sizeof(unsigned), c->stream);
     if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync query ray counter");
-    const int form = (c->choice.wide ? 4 : 0) | (ovf ? 2 : 0) | (any ? 1 : 0);
-    switch (form) {
-        case 0: launch_query<false, false, false>(grid, c->stream, S, Q); break;
-        case 1: launch_query<false, false, true>(grid, c->stream, S, Q); break;
-        case 2: launch_query<false, true, false>(grid, c->stream, S, Q); break;
-        case 3: launch_query<false, true, true>(grid, c->stream, S, Q); break;
-        case 4: launch_query<true, false, false>(grid, c->stream, S, Q); break;
-        case 5: launch_query<true, false, true>(grid, c->stream, S, Q); break;
-        case 6: launch_query<true, true, false>(grid, c->stream, S, Q); break;
-        default: launch_query<true, true, true>(grid, c->stream, S, Q); break;
-    }
-    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "query kernel launch");
-    if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) {
-        c->failed = true;
-        return hip_fail(e, "query kernel");
-    }
-    return JT_OK;
+    with_bools(c->choice.wide, ovf, any, [&](auto wide, auto over, auto occ) {
+        hipLaunchKernelGGL((jtk::query_kernel<wide(), over(), occ()>), dim3((unsigned)grid), dim3(BLOCK), 0, c->stream, S, Q);
+    });
+    return launch_finish(c, "query kernel");
 }
 
 // the host variants: rays (and instance ids) staged to the device, the results copied back
@@ -224,18 +174,53 @@ int query_host(jt_ctx* c, int64_t n, const float* rays, const int32_t* instance,
     void* const d_rays = c->q_grow[jt_ctx::Q_RAYS];
     void* const d_inst = instance ? c->q_grow[jt_ctx::Q_INST] : nullptr;
     void* const d_out = c->q_grow[jt_ctx::Q_OUT];
-    hipError_t e;
-    if ((e = hipMemcpy(d_rays, rays, N * 6 * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess ||
-        (instance && (e = hipMemcpy(d_inst, instance, N * sizeof(int32_t), hipMemcpyHostToDevice)) != hipSuccess))
-        return hip_fail(e, "hipMemcpy query rays");
-    const int st = any ? jt_occluded_device(c, n, d_rays, d_out) : jt_intersect_device(c, n, d_rays, d_inst, d_out);
-    if (st != JT_OK) return st;
-    if ((e = hipMemcpy(out, d_out, any ? N : N * sizeof(jt_hit), hipMemcpyDeviceToHost)) != hipSuccess)
-        return hip_fail(e, "hipMemcpy query results");
-    return JT_OK;
+    int st;
+    if ((st = copy_in(d_rays, rays, N * 6 * sizeof(float), "hipMemcpy query rays")) ||
+        (instance && (st = copy_in(d_inst, instance, N * sizeof(int32_t), "hipMemcpy query rays"))))
+        return st;
+    if ((st = any ? jt_occluded_device(c, n, d_rays, d_out) : jt_intersect_device(c, n, d_rays, d_inst, d_out))) return st;
+    return copy_out(out, d_out, any ? N : N * sizeof(jt_hit), "hipMemcpy query results");
 }
 
 }  // namespace
+
+// ---- what every call on the caller's own records shares (jt_surface.hip, jt_radiance.hip too)
+int jtc::ray_call_check(const jt_ctx* c, std::initializer_list<NamedArg> args, const char* range_error, const char* misaligned,
+                        const char* multi_error, bool empty, bool* done) {
+    if (done) *done = false;
+    if (!c) return jt::fail(JT_ERR_INVALID, "ctx is NULL");
+    for (const NamedArg& a : args)
+        if (!a.p) return jt::fail(JT_ERR_INVALID, std::string(a.name) + " is NULL");
+    if (range_error) return jt::fail(JT_ERR_INVALID, range_error);
+    if (misaligned) return jt::fail(JT_ERR_INVALID, misaligned);
+    if (empty) {
+        *done = true;
+        return JT_OK;
+    }
+    if (c->multi) return jt::fail(JT_ERR_UNSUPPORTED, multi_error);
+    if (c->failed) return jt::fail(JT_ERR_STATE, "a previous launch failed; jt_reset the context");
+    return JT_OK;
+}
+
+int jtc::launch_finish(jt_ctx* c, const char* what) {
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, (std::string(what) + " launch").c_str());
+    if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) {
+        c->failed = true;
+        return hip_fail(e, what);
+    }
+    return JT_OK;
+}
+
+int jtc::copy_in(void* dst, const void* src, size_t bytes, const char* what) {
+    const hipError_t e = hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice);
+    return e == hipSuccess ? JT_OK : hip_fail(e, what);
+}
+
+int jtc::copy_out(void* dst, const void* src, size_t bytes, const char* what) {
+    const hipError_t e = hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost);
+    return e == hipSuccess ? JT_OK : hip_fail(e, what);
+}
 
 // a buffer of jt_ctx::q_grow of at least `bytes` (the old one is freed first: its content is not kept)
 int jtc::query_grow(jt_ctx* c, int which, size_t bytes, const char* what) {

@@ -1,7 +1,10 @@
 // jt_radiance.hip — the path integrator on the caller's own rays (include/jtrace.h: jt_radiance and
 // its device-pointer variant; DESIGN.md §6g "Radiance along the caller's rays"): the megakernel's
 // integrator (jt_integrator.h: Path, path_hit, naive_hit, light_hit) driven by the ray queries'
-// persistent, refilling grid (jt_intersect.hip) instead of the megakernel's pixel hand-out.
+// persistent, refilling grid instead of the megakernel's pixel hand-out: query_kernel's refill itself
+// (feed_refill, jt_feed.h), its grid, claim size, ray counter and scene (jt_intersect.h; query_setup,
+// query_scene, jt_context.h), and the argument checks, launch tail and staging copies every call on
+// the caller's records shares (ray_call_check, launch_finish, copy_in, copy_out; jt_intersect.hip).
 //
 // The scene is the context's HBM copy (NCACHE) with the general feature mask, no counters, the
 // 16-entry LDS stack ring and, for a scene whose bound exceeds it, the query grid's own HBM overflow
@@ -32,25 +35,21 @@
 // unspecified.
 #include <hip/hip_runtime.h>
 
-#include <string>
-
 #include "jt_context.h"
+#include "jt_feed.h"
 #include "jt_integrator.h"
 #include "jt_radiance.h"
 
 namespace jtk {
 
-using jtq::QUERY_REFILL_LANES;
 using jtq::QUERY_RING;
 
 struct DRadiance {
     const float* rays;      // n x (o, d)
     float4* rgba;           // n means
-    unsigned* counter;      // the next ray to claim (zeroed before the launch)
     long long stream_base;  // ray i draws from stream stream_base + i
-    int n;
-    int s_begin, s_end;  // the samples of every ray, in order
-    unsigned claim;      // rays a wave claims with one atomic (query_claim_rays)
+    int s_begin, s_end;     // the samples of every ray, in order
+    DFeed feed;             // the n rays' hand-out
 };
 
 // trace_sample's prologue (start_path) for ray `ray`: the sample's stream, its four draws, which a
@@ -86,9 +85,7 @@ __global__ __launch_bounds__(BLOCK) JT_RADIANCE_WAVES_ATTR void radiance_kernel(
     constexpr int F = FT_ALL;
     __shared__ int ring[QUERY_RING * BLOCK];
     __shared__ float lane_lds[jtr::RADIANCE_SLOTS * BLOCK];
-    // the texel-decode LUTs into LDS (tex_lut, jt_scene_eval.h)
-    for (int k = threadIdx.x; k < 512; k += BLOCK) tex_lut[k] = k < 256 ? S.srgb_lut[k] : S.byte_lut[k - 256];
-    __syncthreads();
+    stage_tex_lut(S);
     int* const stack = ring + threadIdx.x;
     float* const acc = lane_lds + jtr::RADIANCE_ACC * BLOCK + threadIdx.x;
     int* const cur = reinterpret_cast<int*>(lane_lds + jtr::RADIANCE_SAMPLE * BLOCK + threadIdx.x);
@@ -105,38 +102,18 @@ __global__ __launch_bounds__(BLOCK) JT_RADIANCE_WAVES_ATTR void radiance_kernel(
     T.nxt = W_EMPTY;
     T.nh = 0;
     int ray = -1;  // the lane's ray; -1: none
-    bool drained = false;          // every ray is claimed
-    unsigned wnext = 0, wend = 0;  // the wave's reserve of claimed rays [wnext, wend)
-    for (;;) {
-        // ---- refill (query_kernel's): the k-th lane without a ray takes the k-th ray of the wave's reserve
-        const unsigned long long idle = __builtin_amdgcn_ballot_w64(ray < 0);
-        const int nidle = __popcll(idle);
-        if (nidle == 64 && drained) break;
-        if (!drained && nidle >= QUERY_REFILL_LANES) {
-            if (wnext >= wend) {
-                unsigned base = 0;
-                if ((threadIdx.x & 63) == 0) base = atomicAdd(Q.counter, Q.claim);
-                base = __builtin_amdgcn_readfirstlane(base);
-                wnext = base;
-                wend = base + Q.claim < (unsigned)Q.n ? base + Q.claim : (unsigned)Q.n;  // < 2^32: query_counter_bound
-                drained = base >= (unsigned)Q.n;
-            }
-            if (!drained) {
-                const unsigned avail = wend - wnext, take = (unsigned)nidle < avail ? (unsigned)nidle : avail;
-                const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(idle >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)idle, 0u));
-                if (ray < 0 && rank < take) {
-                    ray = (int)(wnext + rank);
-                    acc[0] = 0.0f;
-                    acc[BLOCK] = 0.0f;
-                    acc[2 * BLOCK] = 0.0f;
-                    acc[3 * BLOCK] = 0.0f;
-                    *cur = Q.s_begin;
-                    radiance_start<F>(P, Q, ray, Q.s_begin, st);
-                    query_start<WIDE>(S, T, st.o, st.d, -1, stack);
-                }
-                wnext += take;
-            }
-        }
+    jtq::WaveReserve reserve;
+    // ---- refill (jt_feed.h): a lane without a ray takes one of the wave's reserve and starts its first sample
+    while (feed_refill(Q.feed, reserve, ray >= 0, [&](int r) {
+        ray = r;
+        acc[0] = 0.0f;
+        acc[BLOCK] = 0.0f;
+        acc[2 * BLOCK] = 0.0f;
+        acc[3 * BLOCK] = 0.0f;
+        *cur = Q.s_begin;
+        radiance_start<F>(P, Q, ray, Q.s_begin, st);
+        query_start<WIDE>(S, T, st.o, st.d, -1, stack);
+    })) {
         // ---- one step kind for the wave (radiance_step); a lane's own sequence of steps is
         // unchanged, it only waits while another kind runs
         const bool wantp = ray >= 0 && T.nprim > 0, wantn = ray >= 0 && wants_node<WIDE>(T);
@@ -198,29 +175,13 @@ namespace {
 
 constexpr int BLOCK = jtk::BLOCK;
 
-template <bool WIDE, bool OVF, int SAMPLER>
-void launch_radiance(int grid, hipStream_t stream, const DScene& S, const jtd::DParams& P, const jtk::DRadiance& Q) {
-    hipLaunchKernelGGL((jtk::radiance_kernel<WIDE, OVF, SAMPLER>), dim3((unsigned)grid), dim3(BLOCK), 0, stream, S, P, Q);
-}
-
-// the checks both entry points share, in the header's order; *done: n == 0, nothing to do
+// the checks both entry points share; *done: n == 0, nothing to do
 int radiance_check(const jt_ctx* c, int64_t n, const void* rays, const char* rays_name, int64_t stream_base, int32_t s0,
                    int32_t s1, const void* out, const char* out_name, bool device, bool* done) {
-    *done = false;
-    if (!c) return jt::fail(JT_ERR_INVALID, "ctx is NULL");
-    if (!rays) return jt::fail(JT_ERR_INVALID, std::string(rays_name) + " is NULL");
-    if (!out) return jt::fail(JT_ERR_INVALID, std::string(out_name) + " is NULL");
-    if (const char* const msg = jtr::radiance_range_error(n, stream_base, s0, s1)) return jt::fail(JT_ERR_INVALID, msg);
-    if (device && ((uintptr_t)out & 15)) return jt::fail(JT_ERR_INVALID, std::string(out_name) + " must be aligned to 16 bytes");
-    if (n == 0) {
-        *done = true;
-        return JT_OK;
-    }
-    if (c->multi)
-        return jt::fail(JT_ERR_UNSUPPORTED,
-                        "jt_radiance is not available on a multi-device context (jt_create_multi): use one context per device");
-    if (c->failed) return jt::fail(JT_ERR_STATE, "a previous launch failed; jt_reset the context");
-    return JT_OK;
+    return ray_call_check(c, {{rays, rays_name}, {out, out_name}}, jtr::radiance_range_error(n, stream_base, s0, s1),
+                          device && ((uintptr_t)out & 15) ? "d_rgba must be aligned to 16 bytes" : nullptr,
+                          "jt_radiance is not available on a multi-device context (jt_create_multi): use one context per device",
+                          n == 0, done);
 }
 
 // n >= 1 rays from device pointers, on the context's stream; returns once the stream is idle
@@ -235,31 +196,17 @@ int radiance_run(jt_ctx* c, int64_t n, const void* d_rays, int64_t stream_base, 
     jtk::DRadiance Q{};
     Q.rays = (const float*)d_rays;
     Q.rgba = (float4*)d_rgba;
-    Q.counter = c->q_counter;
     Q.stream_base = (long long)stream_base;
-    Q.n = (int)n;
     Q.s_begin = s0;
     Q.s_end = s1;
-    Q.claim = (unsigned)jtq::query_claim_rays(n, grid);
-    hipError_t e = hipMemsetAsync(c->q_counter, 0, sizeof(unsigned), c->stream);
+    Q.feed = {c->q_counter, (int)n, (unsigned)jtq::query_claim_rays(n, grid)};
+    const hipError_t e = hipMemsetAsync(c->q_counter, 0, sizeof(unsigned), c->stream);
     if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync radiance ray counter");
-    const int form = (c->choice.wide ? 4 : 0) | (ovf ? 2 : 0) | (c->sampler == 2 ? 1 : 0);
-    switch (form) {
-        case 0: launch_radiance<false, false, 1>(grid, c->stream, S, c->P, Q); break;
-        case 1: launch_radiance<false, false, 2>(grid, c->stream, S, c->P, Q); break;
-        case 2: launch_radiance<false, true, 1>(grid, c->stream, S, c->P, Q); break;
-        case 3: launch_radiance<false, true, 2>(grid, c->stream, S, c->P, Q); break;
-        case 4: launch_radiance<true, false, 1>(grid, c->stream, S, c->P, Q); break;
-        case 5: launch_radiance<true, false, 2>(grid, c->stream, S, c->P, Q); break;
-        case 6: launch_radiance<true, true, 1>(grid, c->stream, S, c->P, Q); break;
-        default: launch_radiance<true, true, 2>(grid, c->stream, S, c->P, Q); break;
-    }
-    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "radiance kernel launch");
-    if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) {
-        c->failed = true;
-        return hip_fail(e, "radiance kernel");
-    }
-    return JT_OK;
+    with_bools(c->choice.wide, ovf, c->sampler == 2, [&](auto wide, auto over, auto naive) {
+        hipLaunchKernelGGL((jtk::radiance_kernel<wide(), over(), naive() ? 2 : 1>), dim3((unsigned)grid), dim3(BLOCK), 0, c->stream, S,
+                           c->P, Q);
+    });
+    return launch_finish(c, "radiance kernel");
 }
 
 }  // namespace
@@ -285,16 +232,14 @@ int jt_radiance(jt_ctx* c, int64_t n, const float* rays, int64_t stream_base, in
     (void)hipSetDevice(c->device);
     const size_t N = (size_t)n;
     // Q_OUT holds a jt_hit (24 bytes) per staged ray: room for a ray's 16-byte mean
-    if (const int st = query_stage(c, n)) return st;
+    int st;
+    if ((st = query_stage(c, n))) return st;
     void* const d_rays = c->q_grow[jt_ctx::Q_RAYS];
     void* const d_out = c->q_grow[jt_ctx::Q_OUT];
-    hipError_t e;
-    if ((e = hipMemcpy(d_rays, rays, N * 6 * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess)
-        return hip_fail(e, "hipMemcpy radiance rays");
-    if (const int st = radiance_run(c, n, d_rays, stream_base, sample_begin, sample_end, d_out)) return st;
-    if ((e = hipMemcpy(rgba, d_out, N * 4 * sizeof(float), hipMemcpyDeviceToHost)) != hipSuccess)
-        return hip_fail(e, "hipMemcpy radiance results");
-    return JT_OK;
+    if ((st = copy_in(d_rays, rays, N * 6 * sizeof(float), "hipMemcpy radiance rays")) ||
+        (st = radiance_run(c, n, d_rays, stream_base, sample_begin, sample_end, d_out)))
+        return st;
+    return copy_out(rgba, d_out, N * 4 * sizeof(float), "hipMemcpy radiance results");
 }
 
 }  // extern "C"

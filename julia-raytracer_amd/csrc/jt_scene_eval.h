@@ -117,6 +117,13 @@ struct __attribute__((aligned(4))) TexelPair {
 // by the kernels that evaluate textures: a texel's four channel decodes are then LDS reads, not
 // four more vector-memory gathers per texel.
 static __shared__ float tex_lut[512];
+// fills them: every thread of the workgroup, once, before the first eval_texture. The megakernel
+// (trace_body_items, jt_kernels.h) keeps the loop written out: through this function two of its
+// ADAPT instances spill two and four more SGPRs
+__device__ __forceinline__ void stage_tex_lut(const DScene& S) {
+    for (int k = threadIdx.x; k < 512; k += BLOCK) tex_lut[k] = k < 256 ? S.srgb_lut[k] : S.byte_lut[k - 256];
+    __syncthreads();
+}
 __device__ __forceinline__ v4 decode_texel(uchar4 b, const float* lut) {
     return V4(lut[b.x], lut[b.y], lut[b.z], tex_lut[256 + b.w]);
 }

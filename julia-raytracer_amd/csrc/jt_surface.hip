@@ -13,13 +13,14 @@
 // miss record. A lane writes its 24 words as six 16-byte stores.
 // camera_kernel: one pixel per thread; start_path's own prologue (camera_sample) for a sample
 // index, eval_camera at the pixel centre for -1.
-// jt_gbuffer is the three launches camera_kernel, query_kernel (jt_intersect.hip, untouched),
+// jt_gbuffer is the three launches camera_kernel, query_kernel (jt_intersect.hip),
 // surface_kernel in stream order: a lane's query ends at its own time, so an evaluation inlined in
 // the query loop's epilogue would run with a few lanes active, hundreds of times per wave, and add
 // its registers to that kernel's.
+// From jt_intersect.hip (jt_context.h): the argument checks (ray_call_check), the launch tail
+// (launch_finish), the staging buffers and copies (query_stage, query_grow, copy_in, copy_out) and
+// the first call's uploads (query_setup).
 #include <hip/hip_runtime.h>
-
-#include <string>
 
 #include "jt_context.h"
 #include "jt_integrator.h"
@@ -42,9 +43,7 @@ __device__ __forceinline__ float4 bits4(int a, int b, float c, int d) {
 
 __global__ __launch_bounds__(BLOCK) void surface_kernel(DScene S, DSurf Q) {
     constexpr int F = FT_ALL;
-    // the texel-decode LUTs into LDS (tex_lut, jt_scene_eval.h): eval_texture decodes 8-bit texels through them
-    for (int k = threadIdx.x; k < 512; k += BLOCK) tex_lut[k] = k < 256 ? S.srgb_lut[k] : S.byte_lut[k - 256];
-    __syncthreads();
+    stage_tex_lut(S);  // eval_texture decodes 8-bit texels through the LUTs in LDS
     const int i = (int)blockIdx.x * BLOCK + (int)threadIdx.x;  // n <= 2^30 (QUERY_MAX_RAYS)
     if (i >= Q.n) return;
     const int2* const h = reinterpret_cast<const int2*>(Q.hits + (size_t)i * 6);
@@ -109,43 +108,24 @@ static_assert(sizeof(jt_hit) == 24, "surface_kernel reads a jt_hit as three 8-by
 
 bool aligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
-// the checks every entry point shares once its arguments are known to be there, in the header's order
-int surface_context_check(const jt_ctx* c) {
-    if (c->multi)
-        return jt::fail(JT_ERR_UNSUPPORTED,
-                        "surface evaluation and camera rays are not available on a multi-device context (jt_create_multi): use one "
-                        "context per device");
-    if (c->failed) return jt::fail(JT_ERR_STATE, "a previous launch failed; jt_reset the context");
-    return JT_OK;
-}
+constexpr const char* SURFACE_MULTI =
+    "surface evaluation and camera rays are not available on a multi-device context (jt_create_multi): use one "
+    "context per device";
 
 // jt_eval_hits' argument checks (device: the pointers are the device variant's, whose alignment the
 // kernel relies on); *done: n == 0, nothing to do
 int eval_check(const jt_ctx* c, int64_t n, const void* rays, const char* rays_name, const void* hits, const char* hits_name,
                const void* out, const char* out_name, bool device, bool* done) {
-    *done = false;
-    if (!c) return jt::fail(JT_ERR_INVALID, "ctx is NULL");
-    if (!rays) return jt::fail(JT_ERR_INVALID, std::string(rays_name) + " is NULL");
-    if (!hits) return jt::fail(JT_ERR_INVALID, std::string(hits_name) + " is NULL");
-    if (!out) return jt::fail(JT_ERR_INVALID, std::string(out_name) + " is NULL");
-    if (n < 0) return jt::fail(JT_ERR_INVALID, "n must be at least 0");
-    if (n > jtq::QUERY_MAX_RAYS) return jt::fail(JT_ERR_INVALID, "n must be at most 2^30 records");
-    if (device && (!aligned(rays, 4) || !aligned(hits, 8) || !aligned(out, 16)))
-        return jt::fail(JT_ERR_INVALID, "d_rays, d_hits and d_out must be aligned to 4, 8 and 16 bytes");
-    if (n == 0) {
-        *done = true;
-        return JT_OK;
-    }
-    return surface_context_check(c);
+    const bool ok = !device || (aligned(rays, 4) && aligned(hits, 8) && aligned(out, 16));
+    return ray_call_check(c, {{rays, rays_name}, {hits, hits_name}, {out, out_name}},
+                          jtq::query_count_error(n, "n must be at most 2^30 records"),
+                          ok ? nullptr : "d_rays, d_hits and d_out must be aligned to 4, 8 and 16 bytes", SURFACE_MULTI, n == 0, done);
 }
 
 // jt_camera_rays' and jt_gbuffer's; misaligned: nullptr, or what the device variant's pointers fail
 int camera_check(const jt_ctx* c, int32_t sample, const void* out, const char* out_name, const char* misaligned = nullptr) {
-    if (!c) return jt::fail(JT_ERR_INVALID, "ctx is NULL");
-    if (!out) return jt::fail(JT_ERR_INVALID, std::string(out_name) + " is NULL");
-    if (sample < -1) return jt::fail(JT_ERR_INVALID, "sample must be at least -1 (-1: the pixel centres)");
-    if (misaligned) return jt::fail(JT_ERR_INVALID, misaligned);
-    return surface_context_check(c);
+    return ray_call_check(c, {{out, out_name}}, sample < -1 ? "sample must be at least -1 (-1: the pixel centres)" : nullptr, misaligned,
+                          SURFACE_MULTI);
 }
 
 // the first surface call's upload: the element count of every instance's shape
@@ -158,16 +138,6 @@ int surface_setup(jt_ctx* c) {
     const hipError_t e = ni ? hipMemcpy(a, c->inst_nelem.data(), ni * sizeof(int), hipMemcpyHostToDevice) : hipSuccess;
     if (e != hipSuccess) return hip_fail(e, "hipMemcpy surface element counts");
     c->s_nelem = (int*)a;
-    return JT_OK;
-}
-
-int finish(jt_ctx* c, const char* what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, (std::string(what) + " launch").c_str());
-    if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) {
-        c->failed = true;
-        return hip_fail(e, what);
-    }
     return JT_OK;
 }
 
@@ -185,14 +155,14 @@ int surface_run(jt_ctx* c, int64_t n, const void* d_rays, const void* d_hits, vo
     Q.ninst = (int)c->inst_new.size();
     const unsigned grid = (unsigned)((n + BLOCK - 1) / BLOCK);
     hipLaunchKernelGGL(jtk::surface_kernel, dim3(grid), dim3(BLOCK), 0, c->stream, c->S, Q);
-    return finish(c, "surface kernel");
+    return launch_finish(c, "surface kernel");
 }
 
 int camera_run(jt_ctx* c, int32_t sample, void* d_rays) {
     (void)hipSetDevice(c->device);
     const unsigned grid = (unsigned)(((int64_t)c->width * c->height + BLOCK - 1) / BLOCK);
     hipLaunchKernelGGL(jtk::camera_kernel, dim3(grid), dim3(BLOCK), 0, c->stream, c->P, (int)sample, (float2*)d_rays);
-    return finish(c, "camera kernel");
+    return launch_finish(c, "camera kernel");
 }
 
 // the staging of n jt_surface records
@@ -203,11 +173,6 @@ int surface_stage(jt_ctx* c, int64_t n) {
     if (const int st = query_grow(c, jt_ctx::Q_SURF, (size_t)cap * sizeof(jt_surface), "surface records")) return st;
     c->q_stage_surf = cap;
     return JT_OK;
-}
-
-int copy_out(void* dst, const void* src, size_t bytes, const char* what) {
-    const hipError_t e = hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost);
-    return e == hipSuccess ? JT_OK : hip_fail(e, what);
 }
 
 }  // namespace
@@ -256,11 +221,10 @@ int jt_eval_hits(jt_ctx* c, int64_t n, const float* rays, const jt_hit* hits, jt
     void* const d_hits = c->q_grow[jt_ctx::Q_OUT];
     void* const d_out = c->q_grow[jt_ctx::Q_SURF];
     const size_t N = (size_t)n;
-    hipError_t e;
-    if ((e = hipMemcpy(d_rays, rays, N * 6 * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(d_hits, hits, N * sizeof(jt_hit), hipMemcpyHostToDevice)) != hipSuccess)
-        return hip_fail(e, "hipMemcpy surface rays and hits");
-    if ((st = surface_run(c, n, d_rays, d_hits, d_out))) return st;
+    if ((st = copy_in(d_rays, rays, N * 6 * sizeof(float), "hipMemcpy surface rays and hits")) ||
+        (st = copy_in(d_hits, hits, N * sizeof(jt_hit), "hipMemcpy surface rays and hits")) ||
+        (st = surface_run(c, n, d_rays, d_hits, d_out)))
+        return st;
     return copy_out(out, d_out, N * sizeof(jt_surface), "hipMemcpy surface records");
 }
 

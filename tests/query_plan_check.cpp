@@ -7,10 +7,11 @@
 //   - query_ovf_entries: every lane's area [slot * need, slot * need + need) of the grid lies inside
 //     it, also at the largest grid and bound (no 32-bit wrap);
 //   - query_claim_rays: a power of two in [64, QUERY_CLAIM_MAX], above 64 only while every wave of
-//     the grid can have a claim; and the refill's hand-out, replayed: waves that claim that many
-//     consecutive rays with one add, hand them to their idle lanes and stop at the first claim
-//     starting at or past n hand every ray out exactly once, whatever the order of the refills, and
-//     the counter stays below query_counter_bound (< 2^32);
+//     the grid can have a claim; and the refill's hand-out, run on jtq::WaveReserve, the struct the
+//     kernels' refill runs (csrc/jt_feed.h): waves that claim that many consecutive rays with one
+//     add, hand them to their idle lanes and stop at the first claim starting at or past n hand
+//     every ray out exactly once, whatever the order of the refills, and the counter stays below
+//     query_counter_bound (< 2^32);
 //   - query_stage_rays: enough for the call, unchanged while the call fits, at least doubling when
 //     it grows, a multiple of 1024, never above QUERY_MAX_RAYS.
 #include <cstdint>
@@ -56,38 +57,36 @@ void check_ovf() {
 }
 
 // the waves of query_grid(n, cus) claim query_claim_rays rays at a time and hand them to between
-// QUERY_REFILL_LANES and 64 idle lanes per refill, until each has seen a claim start at or past n;
-// the next wave to refill and its idle lanes come from a small generator (every order is a valid run)
+// QUERY_REFILL_LANES and 64 idle lanes per refill, until each has seen a claim start at or past n:
+// jtq::WaveReserve's members, called as feed_refill (csrc/jt_feed.h) calls them. The next wave to
+// refill and its idle lanes come from a small generator (every order is a valid run)
 void check_claims(int64_t n, int cus, unsigned seed) {
     const int grid = jtq::query_grid(n, cus), waves = grid * (BLOCK / 64);
     const int claim = jtq::query_claim_rays(n, grid);
     check(claim >= 64 && claim <= jtq::QUERY_CLAIM_MAX && (claim & (claim - 1)) == 0, "claim size", n, cus, claim);
     check(claim == 64 || (int64_t)claim * waves <= n, "a claim that leaves waves without rays", n, cus, claim);
     std::vector<int> taken((size_t)n, 0);
-    std::vector<char> drained((size_t)waves, 0);
-    std::vector<uint64_t> wnext((size_t)waves, 0), wend((size_t)waves, 0);
-    uint64_t counter = 0;
+    std::vector<jtq::WaveReserve> reserve((size_t)waves);
+    uint64_t counter = 0;  // 64 bits here, so that a wrap of the kernels' 32-bit counter shows against its bound
     int left = waves;
     unsigned s = seed;
     auto rnd = [&]() { return (s = s * 1664525u + 1013904223u) >> 8; };
     while (left > 0) {
         size_t w = rnd() % (unsigned)waves;
-        while (drained[w]) w = (w + 1) % (size_t)waves;
-        const uint64_t idle = (uint64_t)jtq::QUERY_REFILL_LANES + rnd() % (unsigned)(64 - jtq::QUERY_REFILL_LANES + 1);
-        if (wnext[w] >= wend[w]) {
-            const uint64_t base = counter;
+        while (reserve[w].drained) w = (w + 1) % (size_t)waves;
+        jtq::WaveReserve& r = reserve[w];
+        const unsigned idle = (unsigned)jtq::QUERY_REFILL_LANES + rnd() % (unsigned)(64 - jtq::QUERY_REFILL_LANES + 1);
+        if (r.empty()) {  // feed_refill's atomicAdd
+            r.claimed((unsigned)counter, (unsigned)claim, (unsigned)n);
             counter += (uint64_t)claim;
-            wnext[w] = base;
-            wend[w] = base + (uint64_t)claim < (uint64_t)n ? base + (uint64_t)claim : (uint64_t)n;
-            if (base >= (uint64_t)n) {
-                drained[w] = 1;
+            if (r.drained) {
                 left--;
                 continue;
             }
         }
-        const uint64_t avail = wend[w] - wnext[w], take = idle < avail ? idle : avail;
-        for (uint64_t k = 0; k < take; k++) taken[(size_t)(wnext[w] + k)]++;
-        wnext[w] += take;
+        const unsigned take = r.take(idle);
+        for (unsigned k = 0; k < take; k++) taken[(size_t)(r.next + k)]++;
+        r.next += take;
     }
     long wrong = 0;
     for (int v : taken) wrong += v != 1;

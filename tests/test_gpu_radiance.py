@@ -16,7 +16,8 @@ traversal orders.
 3. The mean over samples: radiance(rays, 3, 8) is the float32 fold, in numpy, of the five one-sample
    calls, acc = acc * (1 - w) + x * w with w = 1 / (c + 1) from 0.
 4. Partition and grid independence: one call on rays[:n] equals two calls on its halves, the second
-   with stream_base advanced, and the first n results do not depend on n.
+   with stream_base advanced, and the first n results do not depend on n. Once at 2.1 M rays, where
+   waves claim and refill many times, blocks of the result equal the small call with their stream_base.
 5. Rays no camera makes: alpha is 1 exactly where jt_intersect reports a hit, a miss is four zero
    words, every value is finite and within [0, params.clamp].
 6. The context is untouched. 7. The device variant gives the host variant's bits.
@@ -188,6 +189,27 @@ def test_partition_and_grid_independence(runs):
     shifted = st.radiance(rays[100:200], 0, 2, stream_base=100)
     assert np.array_equal(bits(shifted), bits(whole[100:200]))
     assert not np.array_equal(bits(st.radiance(rays[100:200], 0, 2)), bits(whole[100:200]))
+    st.close()
+
+
+def test_partition_across_refills(runs):
+    """The refill past a wave's first claim, which the 3015 rays of every other test never reach (each
+    wave claims 64 once). 700 copies of the camera's rays are 2 110 500 rays, more than 4 x 256 x 8 x
+    256 (test_gpu_intersect.py's bound: four rays for every lane of a 256-unit device's persistent
+    grid), and a wave claims 256 at a time: lanes finish a ray and take another, a reserve spans
+    several refills, and the hand-out (csrc/jt_feed.h) runs to its drain inside radiance_kernel.
+    Copy k of the result is the small call with stream_base k * N, in every bit."""
+    COPIES = 700
+    st = runs.get_run("cornell", "near", {}).state()
+    rays = st.camera_rays(0)
+    tiled = np.tile(rays, (COPIES, 1))
+    assert tiled.shape == (COPIES * N, 6) and COPIES * N > 4 * 256 * 8 * 256
+    got = st.radiance(tiled, 0, 1)
+    assert got.shape == (COPIES * N, 4)
+    for k in (0, 1, 349, 699):
+        want = st.radiance(rays, 0, 1, stream_base=k * N)
+        assert (want[:, 3] == 1).sum() > 100
+        assert np.array_equal(bits(got[k * N:(k + 1) * N]), bits(want)), k
     st.close()
 
 
