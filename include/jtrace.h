@@ -700,6 +700,65 @@ int jt_radiance(jt_ctx* ctx, int64_t n, const float* rays /* n x (o, d) */, int6
 int jt_radiance_device(jt_ctx* ctx, int64_t n, const void* d_rays, int64_t stream_base,
                        int32_t sample_begin, int32_t sample_end, void* d_rgba);
 
+/* ---- cosine-weighted gathers at the caller's points --------------------------------------- */
+/* What a lightmap texel, an irradiance probe or an ambient-occlusion map needs: the integrator's
+ * mean over the hemisphere at a point, every sample along a direction of its own. jt_radiance
+ * keeps one ray for all samples of a record; here the direction is drawn per sample, in the
+ * kernel, from the sample's own random stream.
+ * A point record is 6 floats, position then normal: the layout of a ray record.
+ * jt_irradiance: for every point i (points[6 i ..] = position, normal) the running mean of samples
+ * [sample_begin, sample_end), in order. For sample s:
+ *   - rng = rng_init(params.seed, stream_base + i, s), as in jt_radiance;
+ *   - ruv = rand2f(rng), the first of the sample prologue's two draws (the one that picks the image
+ *     position for a camera); the second rand2f is drawn and discarded, so after the prologue
+ *     the stream is exactly where jt_radiance leaves it;
+ *   - o = position, as given; d = sample_hemisphere_cos(normal, ruv), the matte lobe's own function
+ *     (src/shading.jl:716-722): z = sqrt(ruv.y), r = sqrt(1 - z z), phi = 2 pi ruv.x, the local
+ *     direction (r cos phi, r sin phi, z) in basis_fromz(normal), which normalises the normal, and
+ *     the result normalised;
+ *   - from there on everything is jt_radiance's: the path state, the context's sampler, bounces,
+ *     nocaustics, envhidden, clamp and traversal, trace_sample's epilogue, the target (radiance, 1)
+ *     or (0, 0, 0, 0), and acc = acc * (1 - w) + target * w with w = 1 / (float)(c + 1), in float32
+ *     without fused multiply-adds.
+ * rgba[4 i ..] = acc after the last sample.
+ * jt_hemisphere_rays: rays[6 i ..] = exactly that (o, d) of point i for the one sample `sample`:
+ * the position's bits and the direction jt_irradiance draws.
+ * The contract: jt_irradiance(points, base, s, s + 1) is, in every bit,
+ * jt_radiance(jt_hemisphere_rays(points, base, s), base, s, s + 1), and a range is the float32
+ * fold above of its one-sample calls. As in jt_radiance a point's result depends on the point, its
+ * stream and the sample range only: an array split over several calls, stream_base advanced by
+ * the points already done, gives the bits of one call.
+ * What the mean is: the directions have the pdf cos(theta) / pi, so the irradiance at the point
+ * is E = pi * rgb, and a matte surface of albedo rho there sends out rho * rgb. alpha is the share
+ * of gather rays that met a surface or a visible environment; in a scene without an environment,
+ * or with envhidden, 1 - alpha is the cosine-weighted sky visibility: ambient occlusion at
+ * unbounded distance. The gather ray is the integrator's bounce 0: an emitter it sees directly
+ * counts, and max_roughness starts at 0. The origin lies on the caller's surface as given; the
+ * primitive tests' ray_eps keeps the ray from hitting that surface, as it does for the
+ * integrator's own bounce rays. With the six axis normals at one position the result is an
+ * ambient cube.
+ * A zero or non-finite normal or position is the caller's responsibility: every lane still ends
+ * in a bounded number of steps, the result for such a point is unspecified.
+ * Everything else as jt_radiance: the calls read the scene and the parameters only (image, AOVs,
+ * stream means, variance, the adaptive mask and every jt_counters field stay bit for bit as they
+ * were, queued samples stay queued); the *_device variants take device pointers on the context's
+ * device (d_rgba aligned to 16 bytes, d_rays to 8), run on the context's stream and return when it
+ * is idle; the host variants stage through the buffers the ray queries' host variants use.
+ * Errors, in jt_radiance's order and with its messages: JT_ERR_INVALID (naming the argument) for a
+ * NULL ctx, points or output, n < 0 or n > 2^30, stream_base < 0 or stream_base + n > 2^31, then
+ * for jt_irradiance sample_begin < 0, sample_end <= sample_begin, more than 2^24 samples, for
+ * jt_hemisphere_rays sample < 0, then a d_rgba not aligned to 16 bytes or a d_rays not aligned to
+ * 8, before the context is looked at and before anything is written; n == 0 returns JT_OK with no
+ * device work; JT_ERR_UNSUPPORTED for a multi-device context; JT_ERR_STATE for a failed context. */
+int jt_irradiance(jt_ctx* ctx, int64_t n, const float* points /* n x (position, normal) */, int64_t stream_base,
+                  int32_t sample_begin, int32_t sample_end, float* rgba /* n x 4 */);
+int jt_irradiance_device(jt_ctx* ctx, int64_t n, const void* d_points, int64_t stream_base,
+                         int32_t sample_begin, int32_t sample_end, void* d_rgba);
+int jt_hemisphere_rays(jt_ctx* ctx, int64_t n, const float* points, int64_t stream_base, int32_t sample,
+                       float* rays /* n x (o, d) */);
+int jt_hemisphere_rays_device(jt_ctx* ctx, int64_t n, const void* d_points, int64_t stream_base, int32_t sample,
+                              void* d_rays);
+
 /* zero accumulators (at once if their device pointers were handed out, else before they are
  * next read or overwritten), samples = 0, queued samples dropped */
 int jt_reset(jt_ctx* ctx);

@@ -1,4 +1,4 @@
-// jt_radiance.h — the integer rules of a jt_radiance launch (include/jtrace.h: jt_radiance; the
+// jt_radiance.h — the integer rules of a jt_radiance or jt_irradiance launch (include/jtrace.h; the
 // kernel and the context's half are in jt_radiance.hip): the argument bounds, the lane's LDS slots
 // and the step-kind vote of a wave. The grid, the claim size and the overflow area are the ray
 // queries' (jt_intersect.h). Plain C++ (no HIP runtime), shared by jt_radiance.hip and the host
@@ -50,6 +50,11 @@ constexpr int radiance_step(int np, int nn, int ns) {
            : np * jtq::QUERY_VOTE_P >= nn                          ? STEP_PRIM
                                                                    : STEP_NODE;
 }
+
+// Where a sample's ray comes from (radiance_kernel's SOURCE): the caller's ray record as it stands
+// (jt_radiance), or the caller's point record (position, normal) and a cosine-weighted direction
+// about the normal drawn from the sample's own stream (jt_irradiance, jt_hemisphere_rays)
+enum : int { SOURCE_RAY = 0, SOURCE_HEMISPHERE = 1 };
 
 // the argument rules of jt_radiance that do not need the context, in the header's order; nullptr:
 // all hold, else the message

@@ -1,5 +1,7 @@
 // jt_radiance.hip — the path integrator on the caller's own rays (include/jtrace.h: jt_radiance and
-// its device-pointer variant; DESIGN.md §6g "Radiance along the caller's rays"): the megakernel's
+// its device-pointer variant; DESIGN.md §6g "Radiance along the caller's rays") and at the caller's
+// own points, every sample along a cosine-weighted direction of its own (jt_irradiance,
+// jt_hemisphere_rays and their device-pointer variants): the megakernel's
 // integrator (jt_integrator.h: Path, path_hit, naive_hit, light_hit) driven by the ray queries'
 // persistent, refilling grid instead of the megakernel's pixel hand-out: query_kernel's refill itself
 // (feed_refill, jt_feed.h), its grid, claim size, ray counter and scene (jt_intersect.h; query_setup,
@@ -11,7 +13,9 @@
 // area: query_kernel's configuration. A lane takes a ray and keeps it for all its samples: the mean
 // is defined in sample order, so a lane that owns its ray needs no atomics and no second pass. Its
 // running mean, its sample index and the parked path state (Path::pk) live in the lane's LDS slots
-// (jt_radiance.h), the stack ring beside them.
+// (jt_radiance.h), the stack ring beside them. Where a sample's ray comes from is the kernel's
+// compile-time SOURCE (radiance_ray): the record as it stands, or the hemisphere draw about the
+// record's normal; nothing else differs, and hemisphere_kernel writes that same ray out.
 //
 // Each iteration of a wave runs one step kind, chosen by a lane vote (radiance_step):
 //   a primitive step   prim_step
@@ -45,23 +49,36 @@ namespace jtk {
 using jtq::QUERY_RING;
 
 struct DRadiance {
-    const float* rays;      // n x (o, d)
+    const float* rays;      // n x (o, d); SOURCE_HEMISPHERE: n x (position, normal)
     float4* rgba;           // n means
     long long stream_base;  // ray i draws from stream stream_base + i
     int s_begin, s_end;     // the samples of every ray, in order
     DFeed feed;             // the n rays' hand-out
 };
 
-// trace_sample's prologue (start_path) for ray `ray`: the sample's stream, its four draws, which a
-// camera would have used, and the path state; the ray is the caller's
-template <int F>
+// A sample's ray, the one arm radiance_kernel and hemisphere_kernel share: the stream of (record,
+// sample), the sample prologue's four draws, which a camera would have used for the image and the
+// lens position, and (o, d) from record `rec` of `recs`. SOURCE_RAY: the record is the ray and the
+// draws are discarded. SOURCE_HEMISPHERE: the record is (position, normal); o is the position as
+// given and d the matte lobe's own cosine-weighted direction about the normal
+// (sample_hemisphere_cos, jt_bsdf.h) for the first draw, the second discarded. Either way the stream
+// is left after the prologue, where trace_sample's path begins.
+template <int SOURCE>
+__device__ __forceinline__ void radiance_ray(const DParams& P, const float* recs, long long stream_base, int rec, int sample, Rng& rng,
+                                             v3& o, v3& d) {
+    rng = rng_init(P.seed, (int)(stream_base + rec), sample);  // < 2^31: RADIANCE_MAX_STREAM
+    const v2 ruv = rand2f(rng);
+    (void)rand2f(rng);
+    const float* const r = recs + (size_t)rec * 6;
+    o = V3(r[0], r[1], r[2]);
+    d = V3(r[3], r[4], r[5]);
+    if constexpr (SOURCE == jtr::SOURCE_HEMISPHERE) d = sample_hemisphere_cos(d, ruv);
+}
+
+// trace_sample's prologue (start_path) for ray `ray`: the sample's ray (radiance_ray) and the path state
+template <int F, int SOURCE>
 __device__ __forceinline__ void radiance_start(const DParams& P, const DRadiance& Q, int ray, int sample, Path& st) {
-    st.rng = rng_init(P.seed, (int)(Q.stream_base + ray), sample);  // < 2^31: RADIANCE_MAX_STREAM
-    (void)rand2f(st.rng);
-    (void)rand2f(st.rng);
-    const float* const r = Q.rays + (size_t)ray * 6;
-    st.o = V3(r[0], r[1], r[2]);
-    st.d = V3(r[3], r[4], r[5]);
+    radiance_ray<SOURCE>(P, Q.rays, Q.stream_base, ray, sample, st.rng, st.o, st.d);
     st.set_radiance<F>(V3(0, 0, 0));
     st.set_weight<F>(V3(1, 1, 1));
     st.set_max_roughness<F>(0.0f);
@@ -80,7 +97,7 @@ __device__ __forceinline__ int radiance_query_instance(const DScene& S, const Pa
 #define JT_RADIANCE_WAVES_ATTR
 #endif
 
-template <bool WIDE, bool OVF, int SAMPLER>
+template <bool WIDE, bool OVF, int SAMPLER, int SOURCE>
 __global__ __launch_bounds__(BLOCK) JT_RADIANCE_WAVES_ATTR void radiance_kernel(DScene S, DParams P, DRadiance Q) {
     constexpr int F = FT_ALL;
     __shared__ int ring[QUERY_RING * BLOCK];
@@ -111,7 +128,7 @@ __global__ __launch_bounds__(BLOCK) JT_RADIANCE_WAVES_ATTR void radiance_kernel(
         acc[2 * BLOCK] = 0.0f;
         acc[3 * BLOCK] = 0.0f;
         *cur = Q.s_begin;
-        radiance_start<F>(P, Q, ray, Q.s_begin, st);
+        radiance_start<F, SOURCE>(P, Q, ray, Q.s_begin, st);
         query_start<WIDE>(S, T, st.o, st.d, -1, stack);
     })) {
         // ---- one step kind for the wave (radiance_step); a lane's own sequence of steps is
@@ -157,12 +174,28 @@ __global__ __launch_bounds__(BLOCK) JT_RADIANCE_WAVES_ATTR void radiance_kernel(
                     ray = -1;
                 } else {
                     *cur = sample + 1;
-                    radiance_start<F>(P, Q, ray, sample + 1, st);
+                    radiance_start<F, SOURCE>(P, Q, ray, sample + 1, st);
                 }
             }
             if (ray >= 0) query_start<WIDE>(S, T, st.o, st.d, radiance_query_instance(S, st), stack);
         }
     }
+}
+
+// jt_hemisphere_rays: one point per thread on a plain grid, as jt_surface.hip's camera_kernel; the
+// ray radiance_kernel<.., SOURCE_HEMISPHERE> starts sample `sample` of point i with, from the same arm.
+// A thread reads its record before it writes, so rays may be the points' own array.
+__global__ __launch_bounds__(BLOCK) void hemisphere_kernel(DParams P, const float* points, long long stream_base, int sample, int n,
+                                                           float2* rays) {
+    const int i = (int)blockIdx.x * BLOCK + (int)threadIdx.x;  // n <= 2^30 (QUERY_MAX_RAYS)
+    if (i >= n) return;
+    Rng rng;
+    v3 o, d;
+    radiance_ray<jtr::SOURCE_HEMISPHERE>(P, points, stream_base, i, sample, rng, o, d);
+    float2* const y = rays + (size_t)i * 3;
+    y[0] = make_float2(o.x, o.y);
+    y[1] = make_float2(o.z, d.x);
+    y[2] = make_float2(d.y, d.z);
 }
 
 }  // namespace jtk
@@ -175,17 +208,30 @@ namespace {
 
 constexpr int BLOCK = jtk::BLOCK;
 
-// the checks both entry points share; *done: n == 0, nothing to do
-int radiance_check(const jt_ctx* c, int64_t n, const void* rays, const char* rays_name, int64_t stream_base, int32_t s0,
-                   int32_t s1, const void* out, const char* out_name, bool device, bool* done) {
-    return ray_call_check(c, {{rays, rays_name}, {out, out_name}}, jtr::radiance_range_error(n, stream_base, s0, s1),
-                          device && ((uintptr_t)out & 15) ? "d_rgba must be aligned to 16 bytes" : nullptr,
-                          "jt_radiance is not available on a multi-device context (jt_create_multi): use one context per device",
-                          n == 0, done);
+constexpr const char* RADIANCE_MULTI =
+    "jt_radiance, jt_irradiance and jt_hemisphere_rays are not available on a multi-device context (jt_create_multi): use one "
+    "context per device";
+
+// the checks jt_radiance's and jt_irradiance's entry points share (`in`: the rays or the points); *done: n == 0, nothing to do
+int radiance_check(const jt_ctx* c, int64_t n, const void* in, const char* in_name, int64_t stream_base, int32_t s0, int32_t s1,
+                   const void* out, const char* out_name, bool device, bool* done) {
+    return ray_call_check(c, {{in, in_name}, {out, out_name}}, jtr::radiance_range_error(n, stream_base, s0, s1),
+                          device && ((uintptr_t)out & 15) ? "d_rgba must be aligned to 16 bytes" : nullptr, RADIANCE_MULTI, n == 0, done);
 }
 
-// n >= 1 rays from device pointers, on the context's stream; returns once the stream is idle
-int radiance_run(jt_ctx* c, int64_t n, const void* d_rays, int64_t stream_base, int32_t s0, int32_t s1, void* d_rgba) {
+// jt_hemisphere_rays': one sample, which only has to be a stream's (sample >= 0), in the place of jt_radiance's range
+int hemisphere_check(const jt_ctx* c, int64_t n, const void* points, const char* points_name, int64_t stream_base, int32_t sample,
+                     const void* out, const char* out_name, bool device, bool* done) {
+    const char* range = jtr::radiance_range_error(n, stream_base, 0, 1);
+    if (!range && sample < 0) range = "sample must be at least 0";
+    return ray_call_check(c, {{points, points_name}, {out, out_name}}, range,
+                          device && ((uintptr_t)out & 7) ? "d_rays must be aligned to 8 bytes" : nullptr, RADIANCE_MULTI, n == 0, done);
+}
+
+// n >= 1 records (SOURCE_RAY: rays, SOURCE_HEMISPHERE: points) from device pointers, on the context's
+// stream; returns once the stream is idle
+template <int SOURCE>
+int radiance_run(jt_ctx* c, int64_t n, const void* d_recs, int64_t stream_base, int32_t s0, int32_t s1, void* d_rgba) {
     (void)hipSetDevice(c->device);
     int st = query_setup(c);
     if (st != JT_OK) return st;
@@ -194,7 +240,7 @@ int radiance_run(jt_ctx* c, int64_t n, const void* d_rays, int64_t stream_base, 
     bool ovf;
     if ((st = query_scene(c, grid, &S, &ovf)) != JT_OK) return st;
     jtk::DRadiance Q{};
-    Q.rays = (const float*)d_rays;
+    Q.rays = (const float*)d_recs;
     Q.rgba = (float4*)d_rgba;
     Q.stream_base = (long long)stream_base;
     Q.s_begin = s0;
@@ -203,16 +249,40 @@ int radiance_run(jt_ctx* c, int64_t n, const void* d_rays, int64_t stream_base, 
     const hipError_t e = hipMemsetAsync(c->q_counter, 0, sizeof(unsigned), c->stream);
     if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync radiance ray counter");
     with_bools(c->choice.wide, ovf, c->sampler == 2, [&](auto wide, auto over, auto naive) {
-        hipLaunchKernelGGL((jtk::radiance_kernel<wide(), over(), naive() ? 2 : 1>), dim3((unsigned)grid), dim3(BLOCK), 0, c->stream, S,
-                           c->P, Q);
+        hipLaunchKernelGGL((jtk::radiance_kernel<wide(), over(), naive() ? 2 : 1, SOURCE>), dim3((unsigned)grid), dim3(BLOCK), 0, c->stream,
+                           S, c->P, Q);
     });
-    return launch_finish(c, "radiance kernel");
+    return launch_finish(c, SOURCE == jtr::SOURCE_RAY ? "radiance kernel" : "irradiance kernel");
+}
+
+// the host variants of both: the records staged in Q_RAYS, the means in Q_OUT, whose jt_hit slot
+// (24 bytes) has room for a 16-byte mean
+template <int SOURCE>
+int radiance_host(jt_ctx* c, int64_t n, const float* recs, int64_t stream_base, int32_t s0, int32_t s1, float* rgba) {
+    (void)hipSetDevice(c->device);
+    const size_t N = (size_t)n;
+    int st;
+    if ((st = query_stage(c, n))) return st;
+    void* const d_recs = c->q_grow[jt_ctx::Q_RAYS];
+    void* const d_out = c->q_grow[jt_ctx::Q_OUT];
+    if ((st = copy_in(d_recs, recs, N * 6 * sizeof(float), "hipMemcpy radiance rays")) ||
+        (st = radiance_run<SOURCE>(c, n, d_recs, stream_base, s0, s1, d_out)))
+        return st;
+    return copy_out(rgba, d_out, N * 4 * sizeof(float), "hipMemcpy radiance results");
+}
+
+int hemisphere_run(jt_ctx* c, int64_t n, const void* d_points, int64_t stream_base, int32_t sample, void* d_rays) {
+    (void)hipSetDevice(c->device);
+    const unsigned grid = (unsigned)((n + BLOCK - 1) / BLOCK);
+    hipLaunchKernelGGL(jtk::hemisphere_kernel, dim3(grid), dim3(BLOCK), 0, c->stream, c->P, (const float*)d_points, (long long)stream_base,
+                       (int)sample, (int)n, (float2*)d_rays);
+    return launch_finish(c, "hemisphere kernel");
 }
 
 }  // namespace
 
 static_assert(jtr::RADIANCE_LDS_BYTES <= 64 * 1024, "radiance_kernel's static LDS");
-static_assert(sizeof(jt_hit) >= 4 * sizeof(float), "the host variant stages a ray's mean in its jt_hit slot of Q_OUT");
+static_assert(sizeof(jt_hit) >= 6 * sizeof(float), "the host variants stage a mean (16 bytes) or a ray (24) in a jt_hit slot of Q_OUT");
 
 extern "C" {
 
@@ -221,25 +291,53 @@ int jt_radiance_device(jt_ctx* c, int64_t n, const void* d_rays, int64_t stream_
     bool done;
     if (const int st = radiance_check(c, n, d_rays, "d_rays", stream_base, sample_begin, sample_end, d_rgba, "d_rgba", true, &done))
         return st;
-    return done ? JT_OK : radiance_run(c, n, d_rays, stream_base, sample_begin, sample_end, d_rgba);
+    return done ? JT_OK : radiance_run<jtr::SOURCE_RAY>(c, n, d_rays, stream_base, sample_begin, sample_end, d_rgba);
 }
 
 int jt_radiance(jt_ctx* c, int64_t n, const float* rays, int64_t stream_base, int32_t sample_begin, int32_t sample_end,
                 float* rgba) {
     bool done;
     if (const int st = radiance_check(c, n, rays, "rays", stream_base, sample_begin, sample_end, rgba, "rgba", false, &done)) return st;
+    return done ? JT_OK : radiance_host<jtr::SOURCE_RAY>(c, n, rays, stream_base, sample_begin, sample_end, rgba);
+}
+
+int jt_irradiance_device(jt_ctx* c, int64_t n, const void* d_points, int64_t stream_base, int32_t sample_begin, int32_t sample_end,
+                         void* d_rgba) {
+    bool done;
+    if (const int st = radiance_check(c, n, d_points, "d_points", stream_base, sample_begin, sample_end, d_rgba, "d_rgba", true, &done))
+        return st;
+    return done ? JT_OK : radiance_run<jtr::SOURCE_HEMISPHERE>(c, n, d_points, stream_base, sample_begin, sample_end, d_rgba);
+}
+
+int jt_irradiance(jt_ctx* c, int64_t n, const float* points, int64_t stream_base, int32_t sample_begin, int32_t sample_end,
+                  float* rgba) {
+    bool done;
+    if (const int st = radiance_check(c, n, points, "points", stream_base, sample_begin, sample_end, rgba, "rgba", false, &done))
+        return st;
+    return done ? JT_OK : radiance_host<jtr::SOURCE_HEMISPHERE>(c, n, points, stream_base, sample_begin, sample_end, rgba);
+}
+
+int jt_hemisphere_rays_device(jt_ctx* c, int64_t n, const void* d_points, int64_t stream_base, int32_t sample, void* d_rays) {
+    bool done;
+    if (const int st = hemisphere_check(c, n, d_points, "d_points", stream_base, sample, d_rays, "d_rays", true, &done)) return st;
+    return done ? JT_OK : hemisphere_run(c, n, d_points, stream_base, sample, d_rays);
+}
+
+int jt_hemisphere_rays(jt_ctx* c, int64_t n, const float* points, int64_t stream_base, int32_t sample, float* rays) {
+    bool done;
+    if (const int st = hemisphere_check(c, n, points, "points", stream_base, sample, rays, "rays", false, &done)) return st;
     if (done) return JT_OK;
     (void)hipSetDevice(c->device);
-    const size_t N = (size_t)n;
-    // Q_OUT holds a jt_hit (24 bytes) per staged ray: room for a ray's 16-byte mean
+    // the points staged in Q_RAYS, the rays in Q_OUT: a ray record fits its 24-byte jt_hit slot
     int st;
     if ((st = query_stage(c, n))) return st;
-    void* const d_rays = c->q_grow[jt_ctx::Q_RAYS];
-    void* const d_out = c->q_grow[jt_ctx::Q_OUT];
-    if ((st = copy_in(d_rays, rays, N * 6 * sizeof(float), "hipMemcpy radiance rays")) ||
-        (st = radiance_run(c, n, d_rays, stream_base, sample_begin, sample_end, d_out)))
+    void* const d_points = c->q_grow[jt_ctx::Q_RAYS];
+    void* const d_rays = c->q_grow[jt_ctx::Q_OUT];
+    const size_t bytes = (size_t)n * 6 * sizeof(float);
+    if ((st = copy_in(d_points, points, bytes, "hipMemcpy hemisphere points")) ||
+        (st = hemisphere_run(c, n, d_points, stream_base, sample, d_rays)))
         return st;
-    return copy_out(rgba, d_out, N * 4 * sizeof(float), "hipMemcpy radiance results");
+    return copy_out(rays, d_rays, bytes, "hipMemcpy hemisphere rays");
 }
 
 }  // extern "C"

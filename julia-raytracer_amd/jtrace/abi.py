@@ -338,6 +338,10 @@ def _declare(lib):
     lib.jt_gbuffer_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.jt_radiance.argtypes = [C.c_void_p, C.c_int64, f32p, C.c_int64, C.c_int32, C.c_int32, f32p]
     lib.jt_radiance_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]
+    lib.jt_irradiance.argtypes = [C.c_void_p, C.c_int64, f32p, C.c_int64, C.c_int32, C.c_int32, f32p]
+    lib.jt_irradiance_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]
+    lib.jt_hemisphere_rays.argtypes = [C.c_void_p, C.c_int64, f32p, C.c_int64, C.c_int32, f32p]
+    lib.jt_hemisphere_rays_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
     lib.jt_reset.argtypes = [C.c_void_p]
     lib.jt_get_device_buffers.argtypes = [C.c_void_p, C.POINTER(jt_device_buffers)]
     lib.jt_set_counters.argtypes = [C.c_void_p, C.c_int32]
@@ -359,6 +363,7 @@ EXPORTED_SYMBOLS = [
     "jt_adapt", "jt_get_sample_counts", "jt_intersect", "jt_occluded", "jt_intersect_device", "jt_occluded_device",
     "jt_eval_hits", "jt_camera_rays", "jt_gbuffer", "jt_eval_hits_device", "jt_camera_rays_device", "jt_gbuffer_device",
     "jt_radiance", "jt_radiance_device",
+    "jt_irradiance", "jt_irradiance_device", "jt_hemisphere_rays", "jt_hemisphere_rays_device",
 ]
 
 

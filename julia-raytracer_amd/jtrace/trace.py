@@ -367,6 +367,43 @@ class TraceState:
                                                  int(sample_begin), int(sample_end), out.ctypes.data_as(abi.f32p)))
         return out
 
+    # --- cosine-weighted gathers at the caller's points (jt_irradiance, jt_hemisphere_rays: include/jtrace.h)
+    def irradiance(self, points, sample_begin: int = 0, sample_end: int = 1, stream_base: int = 0):
+        """jt_irradiance: at every point (n, 6) = (position, normal) the integrator's running mean of
+        samples [sample_begin, sample_end), each along a direction of its own drawn cosine-weighted
+        about the normal from the stream of pixel stream_base + i: (n, 4) float32. pi * rgb is the
+        irradiance, albedo * rgb what a matte surface there sends out, alpha the share of gather
+        rays that met a surface or a visible environment. numpy gives numpy; a torch tensor on the
+        context's device goes zero-copy through jt_irradiance_device and gives a tensor there. One
+        sample s has the bits of radiance(hemisphere_rays(points, s), s, s + 1)."""
+        if hasattr(points, "data_ptr"):
+            torch, n = self._device_rays(points)
+            out = torch.empty((n, 4), dtype=torch.float32, device=points.device)
+            abi.check(self.lib, self.lib.jt_irradiance_device(self.handle, n, points.data_ptr(), int(stream_base),
+                                                              int(sample_begin), int(sample_end), out.data_ptr()))
+            return out
+        points = _host_rays(points)
+        out = np.empty((len(points), 4), np.float32)
+        abi.check(self.lib, self.lib.jt_irradiance(self.handle, len(points), points.ctypes.data_as(abi.f32p), int(stream_base),
+                                                   int(sample_begin), int(sample_end), out.ctypes.data_as(abi.f32p)))
+        return out
+
+    def hemisphere_rays(self, points, sample: int, stream_base: int = 0):
+        """jt_hemisphere_rays: the (n, 6) float32 rays (origin, direction) irradiance starts sample
+        `sample` of every point with: the position's bits and the cosine-weighted direction about
+        the normal. numpy gives numpy, a torch tensor on the context's device a tensor there."""
+        if hasattr(points, "data_ptr"):
+            torch, n = self._device_rays(points)
+            out = torch.empty((n, 6), dtype=torch.float32, device=points.device)
+            abi.check(self.lib, self.lib.jt_hemisphere_rays_device(self.handle, n, points.data_ptr(), int(stream_base), int(sample),
+                                                                   out.data_ptr()))
+            return out
+        points = _host_rays(points)
+        out = np.empty((len(points), 6), np.float32)
+        abi.check(self.lib, self.lib.jt_hemisphere_rays(self.handle, len(points), points.ctypes.data_as(abi.f32p), int(stream_base),
+                                                        int(sample), out.ctypes.data_as(abi.f32p)))
+        return out
+
     def counters(self) -> dict:
         c = abi.jt_counters()
         abi.check(self.lib, self.lib.jt_get_counters(self.handle, C.byref(c)))
