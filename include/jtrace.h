@@ -24,7 +24,10 @@
  *   jt_adapt           (the build's own) adaptive sampling: 8x8 tiles whose variance meets a noise
  *                      target take no more samples; jt_get_sample_counts the samples per pixel
  *   jt_intersect       ~ intersect_scene_bvh / intersect_instance_bvh (src/bvh.jl:306-520) for the
- *                      caller's own rays on the context's scene; jt_occluded its find_any form
+ *                      caller's own rays on the context's scene; jt_occluded its find_any form;
+ *                      jt_intersect_bounded, jt_occluded_bounded the same of Ray3f(o, d, ray_eps, tmax),
+ *                      jt_visible of a segment; jt_ambient_occlusion the share of a point's
+ *                      hemisphere draws that meet nothing within a radius
  *   jt_eval_hits       ~ eval_shading_position / eval_shading_normal / eval_material (src/scene.jl:416-673)
  *                      at the caller's hit records; jt_camera_rays ~ sample_camera (src/trace.jl:651-674);
  *                      jt_gbuffer the two around jt_intersect: the surface under every pixel
@@ -565,8 +568,9 @@ typedef struct jt_hit {      /* 24 bytes */
  * instance[i] >= 0, of intersect_instance_bvh of that instance. It runs in the traversal the
  * context was created with (reference, near or wide, JT_TRAVERSAL_AUTO as resolved), the re-run
  * of an exact-t tie included: the hit the integrator would find for that ray, bit for bit, whatever
- * the number of rays and their order. Rays are unbounded, as every query of the reference is:
- * tmax is infinite, tmin is the reference's ray_eps inside the primitive tests. The direction
+ * the number of rays and their order. Rays are unbounded, as every query of the reference's
+ * integrator is: tmax is infinite (jt_intersect_bounded below takes a bound), tmin is the
+ * reference's ray_eps inside the primitive tests. The direction
  * need not be normalised; t is in units of it.
  * jt_occluded: find_any = true reduced to its flag. A ray's query ends at its first accepted hit
  * and is never re-run for a tie. Until a hit is accepted tmax is infinite, exactly as in the
@@ -594,6 +598,48 @@ int jt_intersect(jt_ctx* ctx, int64_t n, const float* rays /* n x (o, d), 6 floa
 int jt_occluded(jt_ctx* ctx, int64_t n, const float* rays, uint8_t* occluded /* n */);
 int jt_intersect_device(jt_ctx* ctx, int64_t n, const void* d_rays, const void* d_instance, void* d_hits);
 int jt_occluded_device(jt_ctx* ctx, int64_t n, const void* d_rays, void* d_occluded);
+
+/* ---- bounded ray queries ------------------------------------------------------------------ */
+/* The same queries on a ray with an end: a shadow ray to a point light, line of sight between two
+ * points, probe-to-probe links. The reference's Ray3f carries tmin and tmax (src/geometry.jl:36-46),
+ * its box and primitive tests read ray.tmax, transform_ray keeps it and intersect_scene_bvh shrinks
+ * it as hits are accepted (src/bvh.jl:363): a bounded query is the reference's own function called
+ * with Ray3f(o, d, ray_eps, tmax). There is no per-ray tmin: ray_eps is a literal of every step.
+ * jt_intersect_bounded: jt_intersect with ray i's query started at tmax = tmax[i] instead of +inf:
+ * intersect_scene_bvh / intersect_instance_bvh of Ray3f(o, d, ray_eps, tmax[i]), in the context's
+ * traversal. A hit is accepted iff ray_eps <= t <= (current tmax): a hit exactly at the bound
+ * counts. The caller's bound is the current tmax for the tie rule: a near-first query (near or
+ * wide) whose accepted hit lies exactly on it is an exact-t tie like any other, and is run again
+ * in the reference's child order with the same bound. A miss is the unbounded miss record
+ * (t = +inf, ids -1, u = v = 0). tmax NULL, or tmax[i] = +inf, gives the bits of jt_intersect. A
+ * bound below ray_eps, zero or negative, yields a miss by the rule itself. A NaN bound is the
+ * caller's responsibility: the result is unspecified, and the lane still ends in a bounded number
+ * of steps. Everything else as jt_intersect: the instance numbering, "whatever the number of rays
+ * and their order", the host instance[i] range check, t in units of the direction.
+ * jt_occluded_bounded: find_any on the same bounded ray. jt_occluded's prefix argument carries
+ * over unchanged: until a hit is accepted both queries hold the same tmax, namely the bound, so
+ * they take the same steps in the same order up to that hit, and occluded[i] equals the hit flag
+ * of jt_intersect_bounded for every ray in every traversal.
+ * jt_visible: for every segment i (segments[6 i ..] = a, b) the any-hit query of the ray
+ * (a, b - a), the subtraction one float32 operation per component, with the bound 1.0f - ray_eps
+ * (float32); visible[i] = 1 iff nothing is hit. t is in units of the segment, so both ends get
+ * the same relative epsilon: a surface through a (t < ray_eps) or through b (t > 1 - ray_eps) does
+ * not hide the one from the other. By definition the result is 1 - jt_occluded_bounded of those
+ * rays and that bound, bit for bit. a == b, a zero direction, is the caller's responsibility.
+ * The *_device variants take device pointers on the context's device (d_tmax and d_instance may
+ * be NULL), run on the context's stream and return when it is idle. The host variants stage
+ * through the buffers the ray queries' host variants use, the bounds in one more of them.
+ * The context is read only, as for jt_intersect: image, AOVs, stream means, variance, the adaptive
+ * mask and every jt_counters field stay bit for bit, queued samples stay queued.
+ * Errors: jt_intersect's, in its order and with its messages (the segments and the flags named
+ * `segments` and `visible`). */
+int jt_intersect_bounded(jt_ctx* ctx, int64_t n, const float* rays, const float* tmax /* n, or NULL */,
+                         const int32_t* instance /* or NULL */, jt_hit* hits);
+int jt_occluded_bounded(jt_ctx* ctx, int64_t n, const float* rays, const float* tmax /* n, or NULL */, uint8_t* occluded);
+int jt_visible(jt_ctx* ctx, int64_t n, const float* segments /* n x (a, b), 6 floats */, uint8_t* visible);
+int jt_intersect_bounded_device(jt_ctx* ctx, int64_t n, const void* d_rays, const void* d_tmax, const void* d_instance, void* d_hits);
+int jt_occluded_bounded_device(jt_ctx* ctx, int64_t n, const void* d_rays, const void* d_tmax, void* d_occluded);
+int jt_visible_device(jt_ctx* ctx, int64_t n, const void* d_segments, void* d_visible);
 
 /* ---- the surface at a hit ---------------------------------------------------------------- */
 /* What the integrator evaluates at a hit (src/scene.jl eval_shading_position, eval_shading_normal,
@@ -758,6 +804,39 @@ int jt_hemisphere_rays(jt_ctx* ctx, int64_t n, const float* points, int64_t stre
                        float* rays /* n x (o, d) */);
 int jt_hemisphere_rays_device(jt_ctx* ctx, int64_t n, const void* d_points, int64_t stream_base, int32_t sample,
                               void* d_rays);
+
+/* ---- ambient occlusion within a radius ---------------------------------------------------- */
+/* jt_irradiance's 1 - alpha is ambient occlusion at unbounded distance, which in a closed interior
+ * is full occlusion almost everywhere; an occlusion map wants a radius, and one bit per ray, not a
+ * path. jt_ambient_occlusion: for point i (points[6 i ..] = position, normal) and every sample s of
+ * [sample_begin, sample_end) the ray is exactly jt_hemisphere_rays(points, stream_base, s)'s ray i:
+ * the stream (params.seed, stream_base + i, s), the same two draws, the same
+ * sample_hemisphere_cos. On it runs the any-hit query bounded by `radius`
+ * (jt_occluded_bounded's), in the context's traversal.
+ * visibility[i] = (float)(samples whose query found nothing) / (float)(sample_end - sample_begin):
+ * one float32 division of two integers that are exact in float32 (at most 2^24 samples), so the
+ * value does not depend on the order in which samples finish. One sample is 0.0 or 1.0, namely
+ * 1 - jt_occluded_bounded of jt_hemisphere_rays' rays with the radius as every bound, and a range
+ * is the count of its one-sample calls over their number. A point's result depends on the point,
+ * its stream and the sample range only: an array split over several calls, stream_base advanced by
+ * the points already done, gives the bits of one call.
+ * radius must be > 0; +inf is allowed and means unbounded. The directions have unit length, so the
+ * radius is a distance in the scene's units.
+ * The *_device variant takes device pointers on the context's device (d_visibility aligned to 4
+ * bytes), runs on the context's stream and returns when it is idle; the host variant stages through
+ * the buffers the ray queries' host variants use. The context is read only: image, AOVs, stream
+ * means, variance, the adaptive mask and every jt_counters field stay bit for bit, queued samples
+ * stay queued.
+ * Errors, in jt_radiance's order and with its messages: JT_ERR_INVALID (naming the argument) for a
+ * NULL ctx, points or output, n < 0 or n > 2^30, stream_base < 0 or stream_base + n > 2^31,
+ * sample_begin < 0, sample_end <= sample_begin, more than 2^24 samples, then a radius that is NaN
+ * or <= 0, then a misaligned d_visibility, before the context is looked at and before anything is
+ * written; n == 0 returns JT_OK with no device work; JT_ERR_UNSUPPORTED for a multi-device
+ * context; JT_ERR_STATE for a failed context. */
+int jt_ambient_occlusion(jt_ctx* ctx, int64_t n, const float* points /* n x (position, normal) */, int64_t stream_base,
+                         int32_t sample_begin, int32_t sample_end, float radius, float* visibility /* n */);
+int jt_ambient_occlusion_device(jt_ctx* ctx, int64_t n, const void* d_points, int64_t stream_base,
+                                int32_t sample_begin, int32_t sample_end, float radius, void* d_visibility);
 
 /* zero accumulators (at once if their device pointers were handed out, else before they are
  * next read or overwritten), samples = 0, queued samples dropped */

@@ -106,13 +106,14 @@ struct jt_ctx {
     // (jt_eval_hits, jt_camera_rays, jt_gbuffer; jt_surface.hip) stage rays and hits in the same
     // buffers and their jt_surface records in Q_SURF (q_stage_surf records); jt_radiance
     // (jt_radiance.hip) launches on the same counter and overflow area and stages its rays in
-    // Q_RAYS and its means in Q_OUT
+    // Q_RAYS and its means in Q_OUT; the bounded queries (jt_intersect_bounded, jt_occluded_bounded)
+    // stage their per-ray bounds in Q_TMAX, grown with the rays
     std::vector<int> inst_new;
     int* q_to_dev = nullptr;
     int* q_to_ref = nullptr;
     unsigned* q_counter = nullptr;
-    enum { Q_OVF = 0, Q_RAYS, Q_INST, Q_OUT, Q_SURF, Q_NGROW };
-    void* q_grow[Q_NGROW] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    enum { Q_OVF = 0, Q_RAYS, Q_INST, Q_OUT, Q_SURF, Q_TMAX, Q_NGROW };
+    void* q_grow[Q_NGROW] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     size_t q_ovf_entries = 0;
     long long q_stage_rays = 0;
     long long q_stage_surf = 0;

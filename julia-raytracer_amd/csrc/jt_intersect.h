@@ -77,6 +77,15 @@ constexpr const char* query_count_error(int64_t n, const char* most) {
     return n < 0 ? "n must be at least 0" : n > QUERY_MAX_RAYS ? most : nullptr;
 }
 
+// Where a query's starting tmax comes from (query_kernel's BOUND): +inf as every query of the
+// integrator (jt_intersect, jt_occluded), the caller's per-ray array (jt_intersect_bounded,
+// jt_occluded_bounded), or the segment form of jt_visible: the record is (a, b), the ray
+// (a, b - a) and the bound SEGMENT_TMAX for every ray
+enum : int { BOUND_NONE = 0, BOUND_ARRAY = 1, BOUND_SEGMENT = 2 };
+// jt_visible's bound in units of the segment: 1 - ray_eps in float32 (jt_device.h's ray_eps; the
+// kernel's unit asserts the two agree), so both ends keep the same relative epsilon
+constexpr float SEGMENT_TMAX = 1.0f - 0.0001f;
+
 // Rays the staging buffers hold after a call of n rays when they held `have`: unchanged while n
 // fits; else at least twice as many (so m growing calls copy O(m) buffers' worth), rounded up to
 // 1024 rays, at most QUERY_MAX_RAYS.

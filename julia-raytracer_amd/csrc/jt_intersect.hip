@@ -25,6 +25,20 @@
 // rays) bound the whole launch to 2.4 ms whatever the scene (EXPERIMENTS.md). Each iteration then
 // runs one step kind, primitive tests or node steps, picked by the megakernel's biased lane vote.
 // A lane writes its ray's record when its query ends.
+//
+// Bounded queries (jt_intersect_bounded, jt_occluded_bounded, jt_visible): the loop's
+// compile-time BOUND (jt_intersect.h). A bounded query is the same query started at the caller's
+// tmax instead of +inf: T.tmax is per-lane state that every step already reads, so the bound is one
+// assignment after query_start (query_take), and one more after a tie's re-run, whose query_start
+// resets it. The bound is the current tmax for the tie rule too: a near-first query that accepts a
+// hit exactly on it re-runs like any other exact-t tie. The segment form builds d = b - a in the
+// lane and writes the flag inverted (visible). query_kernel keeps its three parameters and its
+// name, query_bounded_kernel is the same loop (query_loop) with a bound.
+//
+// Ambient occlusion (jt_ambient_occlusion): occlusion_kernel, the any-hit loop on the hemisphere
+// draws of jt_irradiance (radiance_ray, jt_sample_ray.h), bounded by the call's radius. A lane keeps
+// its point for all its samples, as radiance_kernel does, and counts the samples whose query found
+// nothing in a register: no atomics, no second pass, no shading, no per-lane LDS slots.
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -32,6 +46,7 @@
 
 #include "jt_context.h"
 #include "jt_feed.h"
+#include "jt_sample_ray.h"
 #include "jt_traverse.h"
 
 namespace jtk {
@@ -69,9 +84,16 @@ __device__ __forceinline__ void write_hit(const DQuery& Q, int ray, const Hit& h
     y[5] = h.hit ? 1 : 0;
 }
 
+static_assert(jtq::SEGMENT_TMAX == 1.0f - ray_eps, "jt_visible's bound is 1 - ray_eps");
+// the tmax ray `ray`'s bounded query starts at: the caller's, or the segment form's constant
+template <int BOUND>
+__device__ __forceinline__ float query_bound(const float* tmax, int ray) {
+    return BOUND == jtq::BOUND_SEGMENT ? jtq::SEGMENT_TMAX : tmax[ray];
+}
+
 // the lane starts ray `ray`'s query; false: its instance id is out of range, a miss is recorded
-template <bool WIDE, bool ANY>
-__device__ __forceinline__ bool query_take(const DScene& S, const DQuery& Q, Trav& T, int ray, int* stack) {
+template <bool WIDE, bool ANY, int BOUND>
+__device__ __forceinline__ bool query_take(const DScene& S, const DQuery& Q, const float* tmax, Trav& T, int ray, int* stack) {
     const int q = query_instance(Q, ray);
     if (q == Q_BAD_INSTANCE) {
         if (ANY) Q.occ[ray] = 0;
@@ -79,12 +101,21 @@ __device__ __forceinline__ bool query_take(const DScene& S, const DQuery& Q, Tra
         return false;
     }
     const float* const r = Q.rays + (size_t)ray * 6;
-    query_start<WIDE>(S, T, V3(r[0], r[1], r[2]), V3(r[3], r[4], r[5]), q, stack);
+    if constexpr (BOUND == jtq::BOUND_NONE) {
+        query_start<WIDE>(S, T, V3(r[0], r[1], r[2]), V3(r[3], r[4], r[5]), q, stack);
+    } else {
+        const v3 o = V3(r[0], r[1], r[2]);
+        v3 d = V3(r[3], r[4], r[5]);
+        if constexpr (BOUND == jtq::BOUND_SEGMENT) d = d - o;  // the record is (a, b): one float32 subtraction per component
+        query_start<WIDE>(S, T, o, d, q, stack);
+        T.tmax = query_bound<BOUND>(tmax, ray);
+    }
     return true;
 }
 
-template <bool WIDE, bool OVF, bool ANY>
-__global__ __launch_bounds__(BLOCK) void query_kernel(DScene S, DQuery Q) {
+// the loop of query_kernel and query_bounded_kernel; tmax: BOUND_ARRAY's per-ray bounds
+template <bool WIDE, bool OVF, bool ANY, int BOUND>
+__device__ __forceinline__ void query_loop(const DScene& S, const DQuery& Q, const float* tmax) {
     constexpr int F = FT_ALL;
     __shared__ int ring[QUERY_RING * BLOCK];
     int* const stack = ring + threadIdx.x;
@@ -95,7 +126,7 @@ __global__ __launch_bounds__(BLOCK) void query_kernel(DScene S, DQuery Q) {
     jtq::WaveReserve reserve;
     // ---- refill (jt_feed.h): a lane without a ray takes one of the wave's reserve
     while (feed_refill(Q.feed, reserve, ray >= 0, [&](int r) {
-        if (query_take<WIDE, ANY>(S, Q, T, r, stack)) ray = r;
+        if (query_take<WIDE, ANY, BOUND>(S, Q, tmax, T, r, stack)) ray = r;
     })) {
         // ---- one step of every lane with a query in flight: one step kind per iteration, by a
         // biased lane vote (the megakernel's, jt_kernels.h), so the SIMD runs one code path; a lane's
@@ -111,12 +142,97 @@ __global__ __launch_bounds__(BLOCK) void query_kernel(DScene S, DQuery Q) {
         if (ray >= 0) {
             if (ANY) {  // the first accepted hit ends the query; never re-run for a tie
                 if (T.h_inst >= 0 || query_done<WIDE>(T)) {
-                    Q.occ[ray] = T.h_inst >= 0 ? 1 : 0;
+                    // the segment form reports visible: nothing hit
+                    if constexpr (BOUND == jtq::BOUND_SEGMENT) Q.occ[ray] = T.h_inst >= 0 ? 0 : 1;
+                    else Q.occ[ray] = T.h_inst >= 0 ? 1 : 0;
                     ray = -1;
                 }
-            } else if (query_done<WIDE>(T) && !rerun_tie<WIDE>(S, T, T.wo, T.wd, query_instance(Q, ray), stack)) {
-                write_hit(Q, ray, query_hit(T));
+            } else if constexpr (BOUND == jtq::BOUND_NONE) {
+                if (query_done<WIDE>(T) && !rerun_tie<WIDE>(S, T, T.wo, T.wd, query_instance(Q, ray), stack)) {
+                    write_hit(Q, ray, query_hit(T));
+                    ray = -1;
+                }
+            } else if (query_done<WIDE>(T)) {
+                if (rerun_tie<WIDE>(S, T, T.wo, T.wd, query_instance(Q, ray), stack)) {
+                    // the re-run is the same bounded query: its query_start has reset tmax
+                    T.tmax = query_bound<BOUND>(tmax, ray);
+                } else {
+                    // a miss is the unbounded miss record: tmax still holds the bound, t is +inf
+                    Hit h = query_hit(T);
+                    h.t = h.hit ? h.t : __builtin_inff();
+                    write_hit(Q, ray, h);
+                    ray = -1;
+                }
+            }
+        }
+    }
+}
+
+template <bool WIDE, bool OVF, bool ANY>
+__global__ __launch_bounds__(BLOCK) void query_kernel(DScene S, DQuery Q) {
+    query_loop<WIDE, OVF, ANY, jtq::BOUND_NONE>(S, Q, nullptr);
+}
+
+template <bool WIDE, bool OVF, bool ANY, int BOUND>
+__global__ __launch_bounds__(BLOCK) void query_bounded_kernel(DScene S, DQuery Q, const float* tmax) {
+    query_loop<WIDE, OVF, ANY, BOUND>(S, Q, tmax);
+}
+
+struct DOcclusion {
+    const float* points;    // n x (position, normal)
+    float* visibility;      // n quotients
+    long long stream_base;  // point i draws from stream stream_base + i
+    int s_begin, s_end;     // the samples of every point
+    float radius;           // every query's bound; +inf: unbounded
+    DFeed feed;             // the n points' hand-out
+};
+
+// jt_ambient_occlusion: per point and sample the any-hit query of query_loop on jt_hemisphere_rays'
+// ray, bounded by the radius. A sample's outcome is one bit and the quotient is taken once, of two
+// integers, so the value does not depend on when a sample ran.
+template <bool WIDE, bool OVF>
+__global__ __launch_bounds__(BLOCK) void occlusion_kernel(DScene S, DParams P, DOcclusion Q) {
+    constexpr int F = FT_ALL;
+    __shared__ int ring[QUERY_RING * BLOCK];
+    int* const stack = ring + threadIdx.x;
+    const int slot = (int)blockIdx.x * BLOCK + (int)threadIdx.x;  // the lane's HBM stack-overflow area
+    Counters cnt{0, 0, 0, 0};
+    Trav T;
+    int ray = -1;     // the lane's point; -1: none
+    int sample = 0;   // its sample in flight
+    int visible = 0;  // its samples so far whose query found nothing
+    jtq::WaveReserve reserve;
+    // the lane's point starts sample s: the hemisphere draw, then the bounded scene query
+    const auto start = [&](int s) {
+        Rng rng;
+        v3 o, d;
+        radiance_ray<jtr::SOURCE_HEMISPHERE>(P, Q.points, Q.stream_base, ray, s, rng, o, d);
+        query_start<WIDE>(S, T, o, d, -1, stack);
+        T.tmax = Q.radius;
+    };
+    while (feed_refill(Q.feed, reserve, ray >= 0, [&](int r) {
+        ray = r;
+        sample = Q.s_begin;
+        visible = 0;
+        start(sample);
+    })) {
+        // one step kind per iteration, by query_loop's vote
+        const bool wantp = ray >= 0 && T.nprim > 0, wantn = ray >= 0 && T.nprim == 0;
+        const int np = __popcll(__builtin_amdgcn_ballot_w64(wantp)), nn = __popcll(__builtin_amdgcn_ballot_w64(wantn));
+        if (np * QUERY_VOTE_P >= nn) {
+            if (wantp) prim_step<0, F>(S, T, cnt);
+        } else {
+            if (wantn) node_step_any<WIDE, QUERY_RING, OVF, 0, true, F>(S, T, stack, slot, cnt);
+        }
+        // the first accepted hit ends a sample's query; then the next sample, or the quotient
+        if (ray >= 0 && (T.h_inst >= 0 || query_done<WIDE>(T))) {
+            visible += T.h_inst >= 0 ? 0 : 1;
+            sample += 1;
+            if (sample >= Q.s_end) {
+                Q.visibility[ray] = jtr::occlusion_visibility(visible, Q.s_end - Q.s_begin);
                 ray = -1;
+            } else {
+                start(sample);
             }
         }
     }
@@ -140,8 +256,11 @@ int query_check(const jt_ctx* c, int64_t n, const void* rays, const char* rays_n
                           n == 0, done);
 }
 
-// n >= 1 rays from device pointers, on the context's stream; returns once the stream is idle
-int query_run(jt_ctx* c, int64_t n, const void* d_rays, const void* d_inst, void* d_out, bool any) {
+// n >= 1 rays from device pointers, on the context's stream; returns once the stream is idle.
+// bound (jt_intersect.h): BOUND_ARRAY reads d_tmax, BOUND_SEGMENT (any-hit only) takes d_rays as
+// segments and writes visible flags
+int query_run(jt_ctx* c, int64_t n, const void* d_rays, const void* d_inst, void* d_out, bool any, int bound = jtq::BOUND_NONE,
+              const void* d_tmax = nullptr) {
     (void)hipSetDevice(c->device);
     int st = query_setup(c);
     if (st != JT_OK) return st;
@@ -161,25 +280,76 @@ int query_run(jt_ctx* c, int64_t n, const void* d_rays, const void* d_inst, void
     const hipError_t e = hipMemsetAsync(c->q_counter, 0, sizeof(unsigned), c->stream);
     if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync query ray counter");
     with_bools(c->choice.wide, ovf, any, [&](auto wide, auto over, auto occ) {
-        hipLaunchKernelGGL((jtk::query_kernel<wide(), over(), occ()>), dim3((unsigned)grid), dim3(BLOCK), 0, c->stream, S, Q);
+        const dim3 g((unsigned)grid), b(BLOCK);
+        if (bound == jtq::BOUND_NONE) {
+            hipLaunchKernelGGL((jtk::query_kernel<wide(), over(), occ()>), g, b, 0, c->stream, S, Q);
+        } else if (bound == jtq::BOUND_ARRAY) {
+            hipLaunchKernelGGL((jtk::query_bounded_kernel<wide(), over(), occ(), jtq::BOUND_ARRAY>), g, b, 0, c->stream, S, Q,
+                               (const float*)d_tmax);
+        } else if constexpr (occ()) {
+            hipLaunchKernelGGL((jtk::query_bounded_kernel<wide(), over(), true, jtq::BOUND_SEGMENT>), g, b, 0, c->stream, S, Q,
+                               (const float*)nullptr);
+        }
     });
-    return launch_finish(c, "query kernel");
+    return launch_finish(c, bound == jtq::BOUND_NONE ? "query kernel" : "bounded query kernel");
 }
 
-// the host variants: rays (and instance ids) staged to the device, the results copied back
-int query_host(jt_ctx* c, int64_t n, const float* rays, const int32_t* instance, void* out, bool any) {
+// the host variants: rays (and instance ids, and bounds) staged to the device, the results copied back
+int query_host(jt_ctx* c, int64_t n, const float* rays, const int32_t* instance, void* out, bool any, int bound = jtq::BOUND_NONE,
+               const float* tmax = nullptr) {
     (void)hipSetDevice(c->device);
     const size_t N = (size_t)n;
     if (const int st = query_stage(c, n)) return st;
     void* const d_rays = c->q_grow[jt_ctx::Q_RAYS];
     void* const d_inst = instance ? c->q_grow[jt_ctx::Q_INST] : nullptr;
+    void* const d_tmax = tmax ? c->q_grow[jt_ctx::Q_TMAX] : nullptr;
     void* const d_out = c->q_grow[jt_ctx::Q_OUT];
     int st;
     if ((st = copy_in(d_rays, rays, N * 6 * sizeof(float), "hipMemcpy query rays")) ||
-        (instance && (st = copy_in(d_inst, instance, N * sizeof(int32_t), "hipMemcpy query rays"))))
+        (instance && (st = copy_in(d_inst, instance, N * sizeof(int32_t), "hipMemcpy query rays"))) ||
+        (tmax && (st = copy_in(d_tmax, tmax, N * sizeof(float), "hipMemcpy query bounds"))))
         return st;
-    if ((st = any ? jt_occluded_device(c, n, d_rays, d_out) : jt_intersect_device(c, n, d_rays, d_inst, d_out))) return st;
+    if (bound != jtq::BOUND_NONE) st = query_run(c, n, d_rays, d_inst, d_out, any, bound, d_tmax);
+    else st = any ? jt_occluded_device(c, n, d_rays, d_out) : jt_intersect_device(c, n, d_rays, d_inst, d_out);
+    if (st) return st;
     return copy_out(out, d_out, any ? N : N * sizeof(jt_hit), "hipMemcpy query results");
+}
+
+constexpr const char* OCCLUSION_MULTI =
+    "jt_ambient_occlusion is not available on a multi-device context (jt_create_multi): use one context per device";
+
+// jt_ambient_occlusion's checks: jt_radiance's ladder with the radius after the sample range
+int occlusion_check(const jt_ctx* c, int64_t n, const void* points, const char* points_name, int64_t stream_base, int32_t s0, int32_t s1,
+                    float radius, const void* out, const char* out_name, bool device, bool* done) {
+    const char* range = jtr::radiance_range_error(n, stream_base, s0, s1);
+    if (!range) range = jtr::occlusion_radius_error(radius);
+    return ray_call_check(c, {{points, points_name}, {out, out_name}}, range,
+                          device && ((uintptr_t)out & 3) ? "d_visibility must be aligned to 4 bytes" : nullptr, OCCLUSION_MULTI, n == 0, done);
+}
+
+// n >= 1 points from device pointers, on the context's stream; returns once the stream is idle
+int occlusion_run(jt_ctx* c, int64_t n, const void* d_points, int64_t stream_base, int32_t s0, int32_t s1, float radius, void* d_vis) {
+    (void)hipSetDevice(c->device);
+    int st = query_setup(c);
+    if (st != JT_OK) return st;
+    const int grid = jtq::query_grid(n, c->cus);
+    DScene S;
+    bool ovf;
+    if ((st = query_scene(c, grid, &S, &ovf)) != JT_OK) return st;
+    jtk::DOcclusion Q{};
+    Q.points = (const float*)d_points;
+    Q.visibility = (float*)d_vis;
+    Q.stream_base = (long long)stream_base;
+    Q.s_begin = s0;
+    Q.s_end = s1;
+    Q.radius = radius;
+    Q.feed = {c->q_counter, (int)n, (unsigned)jtq::query_claim_rays(n, grid)};
+    const hipError_t e = hipMemsetAsync(c->q_counter, 0, sizeof(unsigned), c->stream);
+    if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync occlusion point counter");
+    with_bools(c->choice.wide, ovf, false, [&](auto wide, auto over, auto) {
+        hipLaunchKernelGGL((jtk::occlusion_kernel<wide(), over()>), dim3((unsigned)grid), dim3(BLOCK), 0, c->stream, S, c->P, Q);
+    });
+    return launch_finish(c, "occlusion kernel");
 }
 
 }  // namespace
@@ -278,7 +448,7 @@ int jtc::query_scene(jt_ctx* c, int grid, DScene* out, bool* ovf) {
     return JT_OK;
 }
 
-// the host variants' staging of rays, instance ids and jt_hit records, grown to hold n rays
+// the host variants' staging of rays, instance ids, bounds and jt_hit records, grown to hold n rays
 int jtc::query_stage(jt_ctx* c, int64_t n) {
     if (n <= c->q_stage_rays) return JT_OK;
     const size_t cap = (size_t)jtq::query_stage_rays(c->q_stage_rays, n);
@@ -286,6 +456,7 @@ int jtc::query_stage(jt_ctx* c, int64_t n) {
     int st;
     if ((st = query_grow(c, jt_ctx::Q_RAYS, cap * 6 * sizeof(float), "query rays")) ||
         (st = query_grow(c, jt_ctx::Q_INST, cap * sizeof(int32_t), "query instance ids")) ||
+        (st = query_grow(c, jt_ctx::Q_TMAX, cap * sizeof(float), "query bounds")) ||
         (st = query_grow(c, jt_ctx::Q_OUT, cap * sizeof(jt_hit), "query results")))
         return st;
     c->q_stage_rays = (long long)cap;
@@ -303,6 +474,17 @@ void jtc::query_free(jt_ctx* c) {
 }
 
 static_assert(sizeof(jt_hit) == 24, "the query kernel writes a jt_hit as six 32-bit words");
+
+// the host variants' check of instance (NULL: none): every id within -1 .. ninstances-1
+static int instance_range_check(const jt_ctx* c, int64_t n, const int32_t* instance) {
+    if (!instance) return JT_OK;
+    const int64_t ni = (int64_t)c->inst_new.size();
+    for (int64_t i = 0; i < n; i++)
+        if (instance[i] < -1 || instance[i] >= ni)
+            return jt::fail(JT_ERR_INVALID, "instance[" + std::to_string(i) + "] = " + std::to_string(instance[i]) +
+                                                " is outside -1 .. " + std::to_string(ni - 1));
+    return JT_OK;
+}
 
 extern "C" {
 
@@ -322,13 +504,7 @@ int jt_intersect(jt_ctx* c, int64_t n, const float* rays, const int32_t* instanc
     bool done;
     if (const int st = query_check(c, n, rays, "rays", hits, "hits", &done)) return st;
     if (done) return JT_OK;
-    if (instance) {
-        const int64_t ni = (int64_t)c->inst_new.size();
-        for (int64_t i = 0; i < n; i++)
-            if (instance[i] < -1 || instance[i] >= ni)
-                return jt::fail(JT_ERR_INVALID, "instance[" + std::to_string(i) + "] = " + std::to_string(instance[i]) +
-                                                    " is outside -1 .. " + std::to_string(ni - 1));
-    }
+    if (const int st = instance_range_check(c, n, instance)) return st;
     return query_host(c, n, rays, instance, hits, false);
 }
 
@@ -336,6 +512,78 @@ int jt_occluded(jt_ctx* c, int64_t n, const float* rays, uint8_t* occluded) {
     bool done;
     if (const int st = query_check(c, n, rays, "rays", occluded, "occluded", &done)) return st;
     return done ? JT_OK : query_host(c, n, rays, nullptr, occluded, true);
+}
+
+// ---- bounded queries: a NULL bound array is the unbounded call itself
+int jt_intersect_bounded_device(jt_ctx* c, int64_t n, const void* d_rays, const void* d_tmax, const void* d_instance, void* d_hits) {
+    if (!d_tmax) return jt_intersect_device(c, n, d_rays, d_instance, d_hits);
+    bool done;
+    if (const int st = query_check(c, n, d_rays, "d_rays", d_hits, "d_hits", &done)) return st;
+    return done ? JT_OK : query_run(c, n, d_rays, d_instance, d_hits, false, jtq::BOUND_ARRAY, d_tmax);
+}
+
+int jt_occluded_bounded_device(jt_ctx* c, int64_t n, const void* d_rays, const void* d_tmax, void* d_occluded) {
+    if (!d_tmax) return jt_occluded_device(c, n, d_rays, d_occluded);
+    bool done;
+    if (const int st = query_check(c, n, d_rays, "d_rays", d_occluded, "d_occluded", &done)) return st;
+    return done ? JT_OK : query_run(c, n, d_rays, nullptr, d_occluded, true, jtq::BOUND_ARRAY, d_tmax);
+}
+
+int jt_visible_device(jt_ctx* c, int64_t n, const void* d_segments, void* d_visible) {
+    bool done;
+    if (const int st = query_check(c, n, d_segments, "d_segments", d_visible, "d_visible", &done)) return st;
+    return done ? JT_OK : query_run(c, n, d_segments, nullptr, d_visible, true, jtq::BOUND_SEGMENT);
+}
+
+int jt_intersect_bounded(jt_ctx* c, int64_t n, const float* rays, const float* tmax, const int32_t* instance, jt_hit* hits) {
+    if (!tmax) return jt_intersect(c, n, rays, instance, hits);
+    bool done;
+    if (const int st = query_check(c, n, rays, "rays", hits, "hits", &done)) return st;
+    if (done) return JT_OK;
+    if (const int st = instance_range_check(c, n, instance)) return st;
+    return query_host(c, n, rays, instance, hits, false, jtq::BOUND_ARRAY, tmax);
+}
+
+int jt_occluded_bounded(jt_ctx* c, int64_t n, const float* rays, const float* tmax, uint8_t* occluded) {
+    if (!tmax) return jt_occluded(c, n, rays, occluded);
+    bool done;
+    if (const int st = query_check(c, n, rays, "rays", occluded, "occluded", &done)) return st;
+    return done ? JT_OK : query_host(c, n, rays, nullptr, occluded, true, jtq::BOUND_ARRAY, tmax);
+}
+
+int jt_visible(jt_ctx* c, int64_t n, const float* segments, uint8_t* visible) {
+    bool done;
+    if (const int st = query_check(c, n, segments, "segments", visible, "visible", &done)) return st;
+    return done ? JT_OK : query_host(c, n, segments, nullptr, visible, true, jtq::BOUND_SEGMENT);
+}
+
+// ---- ambient occlusion
+int jt_ambient_occlusion_device(jt_ctx* c, int64_t n, const void* d_points, int64_t stream_base, int32_t sample_begin,
+                                int32_t sample_end, float radius, void* d_visibility) {
+    bool done;
+    if (const int st = occlusion_check(c, n, d_points, "d_points", stream_base, sample_begin, sample_end, radius, d_visibility,
+                                       "d_visibility", true, &done))
+        return st;
+    return done ? JT_OK : occlusion_run(c, n, d_points, stream_base, sample_begin, sample_end, radius, d_visibility);
+}
+
+int jt_ambient_occlusion(jt_ctx* c, int64_t n, const float* points, int64_t stream_base, int32_t sample_begin, int32_t sample_end,
+                         float radius, float* visibility) {
+    bool done;
+    if (const int st = occlusion_check(c, n, points, "points", stream_base, sample_begin, sample_end, radius, visibility, "visibility",
+                                       false, &done))
+        return st;
+    if (done) return JT_OK;
+    (void)hipSetDevice(c->device);
+    // the points staged in Q_RAYS, the quotients in Q_OUT, whose jt_hit slot has room for one float
+    int st;
+    if ((st = query_stage(c, n))) return st;
+    void* const d_points = c->q_grow[jt_ctx::Q_RAYS];
+    void* const d_vis = c->q_grow[jt_ctx::Q_OUT];
+    if ((st = copy_in(d_points, points, (size_t)n * 6 * sizeof(float), "hipMemcpy occlusion points")) ||
+        (st = occlusion_run(c, n, d_points, stream_base, sample_begin, sample_end, radius, d_vis)))
+        return st;
+    return copy_out(visibility, d_vis, (size_t)n * sizeof(float), "hipMemcpy occlusion results");
 }
 
 }  // extern "C"

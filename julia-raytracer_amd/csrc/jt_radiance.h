@@ -69,4 +69,14 @@ constexpr const char* radiance_range_error(int64_t n, int64_t stream_base, int32
                                                                           : nullptr;
 }
 
+// jt_ambient_occlusion's rules after jt_radiance's range. The radius: greater than 0, +inf allowed
+// (an unbounded query); NaN fails the comparison and is refused with 0 and the negatives.
+constexpr const char* occlusion_radius_error(float radius) {
+    return radius > 0.0f ? nullptr : "radius must be greater than 0 (+inf: unbounded)";
+}
+// The visibility of a point: the samples whose query found nothing over the samples of the call,
+// both exact in float32 (at most RADIANCE_MAX_SAMPLES), one float32 division: a value that does
+// not depend on the order in which the samples finished.
+constexpr float occlusion_visibility(int visible, int samples) { return (float)visible / (float)samples; }
+
 }  // namespace jtr

@@ -14,7 +14,7 @@
 // is defined in sample order, so a lane that owns its ray needs no atomics and no second pass. Its
 // running mean, its sample index and the parked path state (Path::pk) live in the lane's LDS slots
 // (jt_radiance.h), the stack ring beside them. Where a sample's ray comes from is the kernel's
-// compile-time SOURCE (radiance_ray): the record as it stands, or the hemisphere draw about the
+// compile-time SOURCE (radiance_ray, jt_sample_ray.h): the record as it stands, or the hemisphere draw about the
 // record's normal; nothing else differs, and hemisphere_kernel writes that same ray out.
 //
 // Each iteration of a wave runs one step kind, chosen by a lane vote (radiance_step):
@@ -43,6 +43,7 @@
 #include "jt_feed.h"
 #include "jt_integrator.h"
 #include "jt_radiance.h"
+#include "jt_sample_ray.h"
 
 namespace jtk {
 
@@ -55,25 +56,6 @@ struct DRadiance {
     int s_begin, s_end;     // the samples of every ray, in order
     DFeed feed;             // the n rays' hand-out
 };
-
-// A sample's ray, the one arm radiance_kernel and hemisphere_kernel share: the stream of (record,
-// sample), the sample prologue's four draws, which a camera would have used for the image and the
-// lens position, and (o, d) from record `rec` of `recs`. SOURCE_RAY: the record is the ray and the
-// draws are discarded. SOURCE_HEMISPHERE: the record is (position, normal); o is the position as
-// given and d the matte lobe's own cosine-weighted direction about the normal
-// (sample_hemisphere_cos, jt_bsdf.h) for the first draw, the second discarded. Either way the stream
-// is left after the prologue, where trace_sample's path begins.
-template <int SOURCE>
-__device__ __forceinline__ void radiance_ray(const DParams& P, const float* recs, long long stream_base, int rec, int sample, Rng& rng,
-                                             v3& o, v3& d) {
-    rng = rng_init(P.seed, (int)(stream_base + rec), sample);  // < 2^31: RADIANCE_MAX_STREAM
-    const v2 ruv = rand2f(rng);
-    (void)rand2f(rng);
-    const float* const r = recs + (size_t)rec * 6;
-    o = V3(r[0], r[1], r[2]);
-    d = V3(r[3], r[4], r[5]);
-    if constexpr (SOURCE == jtr::SOURCE_HEMISPHERE) d = sample_hemisphere_cos(d, ruv);
-}
 
 // trace_sample's prologue (start_path) for ray `ray`: the sample's ray (radiance_ray) and the path state
 template <int F, int SOURCE>

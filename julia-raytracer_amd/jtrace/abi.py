@@ -342,6 +342,15 @@ def _declare(lib):
     lib.jt_irradiance_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]
     lib.jt_hemisphere_rays.argtypes = [C.c_void_p, C.c_int64, f32p, C.c_int64, C.c_int32, f32p]
     lib.jt_hemisphere_rays_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
+    lib.jt_intersect_bounded.argtypes = [C.c_void_p, C.c_int64, f32p, f32p, i32p, C.POINTER(jt_hit)]
+    lib.jt_occluded_bounded.argtypes = [C.c_void_p, C.c_int64, f32p, f32p, u8p]
+    lib.jt_visible.argtypes = [C.c_void_p, C.c_int64, f32p, u8p]
+    lib.jt_intersect_bounded_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.jt_occluded_bounded_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.jt_visible_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    lib.jt_ambient_occlusion.argtypes = [C.c_void_p, C.c_int64, f32p, C.c_int64, C.c_int32, C.c_int32, C.c_float, f32p]
+    lib.jt_ambient_occlusion_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_float,
+                                                C.c_void_p]
     lib.jt_reset.argtypes = [C.c_void_p]
     lib.jt_get_device_buffers.argtypes = [C.c_void_p, C.POINTER(jt_device_buffers)]
     lib.jt_set_counters.argtypes = [C.c_void_p, C.c_int32]
@@ -364,6 +373,9 @@ EXPORTED_SYMBOLS = [
     "jt_eval_hits", "jt_camera_rays", "jt_gbuffer", "jt_eval_hits_device", "jt_camera_rays_device", "jt_gbuffer_device",
     "jt_radiance", "jt_radiance_device",
     "jt_irradiance", "jt_irradiance_device", "jt_hemisphere_rays", "jt_hemisphere_rays_device",
+    "jt_intersect_bounded", "jt_occluded_bounded", "jt_visible",
+    "jt_intersect_bounded_device", "jt_occluded_bounded_device", "jt_visible_device",
+    "jt_ambient_occlusion", "jt_ambient_occlusion_device",
 ]
 
 

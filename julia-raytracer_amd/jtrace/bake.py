@@ -19,6 +19,13 @@ is the shading normal on the side the element normal points to (--side front) or
 mean, times the surface's colour with --modulate true (what a matte surface there sends out), and
 whose alpha is the coverage. Chart borders are not dilated.
 
+--ao-radius R (a float, or inf) bakes ambient occlusion instead (jt_ambient_occlusion): per point
+the share of the --samples hemisphere draws that meet nothing within R, 1 fully open. --points then
+writes an (n,) float32 array; the lightmap's .npz holds `visibility` (h, w) in the place of `mean`,
+zero at texels no element covers, and the .png is that value as grey, alpha the coverage.
+
+    python -m jtrace.bake --scene scene.json --instance 3 --size 256x256 --samples 64 --ao-radius 0.5 --output ao.png
+
 The sampler, seed and traversal flags are those of `python -m jtrace.radiance`. One line is
 printed: points, samples, milliseconds of the call.
 """
@@ -149,6 +156,8 @@ def _parser() -> argparse.ArgumentParser:
     p.add_argument("--side", choices=["front", "back"], default="front", help="the side of the surface that gathers")
     p.add_argument("--modulate", type=_bool, default=False, help="multiply the .png's rgb by the surface colour")
     p.add_argument("--samples", type=int, default=16, help="number of samples per point")
+    p.add_argument("--ao-radius", type=float, default=None, metavar="R",
+                   help="bake ambient occlusion within this distance (a float or inf) instead of irradiance")
     p.add_argument("--output", type=str, required=True, help="--points: .npy of the means; --instance: .npz or .png")
     p.add_argument("--bounces", type=int, default=8, help="number of bounces")
     p.add_argument("--sampler", type=str, default="path", help="sampler type")
@@ -169,6 +178,9 @@ def _parser() -> argparse.ArgumentParser:
 def run(ns, out=print) -> dict:
     if ns.samples < 1:
         raise SystemExit("--samples must be at least 1")
+    ao = ns.ao_radius is not None
+    if ao and not ns.ao_radius > 0:
+        raise SystemExit("--ao-radius must be greater than 0 (inf: unbounded)")
     ext = os.path.splitext(ns.output)[1].lower()
     lightmap = ns.points is None
     if lightmap and ns.size is None:
@@ -203,7 +215,10 @@ def run(ns, out=print) -> dict:
         covered, surf = instance_points(state, ns.instance, texels, ns.side)
         points = np.concatenate([surf["position"], surf["normal"]], 1).astype(np.float32)
     t0 = time.perf_counter()
-    rgba = state.irradiance(points, 0, ns.samples) if len(points) else np.zeros((0, 4), np.float32)
+    if ao:
+        rgba = state.ambient_occlusion(points, ns.ao_radius, 0, ns.samples) if len(points) else np.zeros(0, np.float32)
+    else:
+        rgba = state.irradiance(points, 0, ns.samples) if len(points) else np.zeros((0, 4), np.float32)
     ms = (time.perf_counter() - t0) * 1e3
     traversal = state.traversal
     state.close()
@@ -212,15 +227,15 @@ def run(ns, out=print) -> dict:
         with open(ns.output, "wb") as f:
             np.save(f, rgba)
     else:
-        mean = np.zeros((h, w, 4), np.float32)
+        mean = np.zeros((h, w) if ao else (h, w, 4), np.float32)
         mean[covered] = rgba
         if ext == ".npz":
             position, normal = np.zeros((h, w, 3), np.float32), np.zeros((h, w, 3), np.float32)
             position[covered], normal[covered] = surf["position"], surf["normal"]
             with open(ns.output, "wb") as f:
-                np.savez(f, mean=mean, covered=covered, position=position, normal=normal)
+                np.savez(f, covered=covered, position=position, normal=normal, **{"visibility" if ao else "mean": mean})
         else:
-            img = mean.copy()
+            img = np.repeat(mean[..., None], 4, axis=2) if ao else mean.copy()
             if ns.modulate:
                 img[covered, :3] *= surf["color"]
             img[..., 3] = covered

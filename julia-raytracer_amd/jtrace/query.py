@@ -6,6 +6,13 @@
 --rays is a .npy file of shape (n, 6), float32: origin and direction per ray (the direction need
 not be normalised; t is in units of it). The output is a .npy file: a structured array with
 jt_hit's fields (instance, element, u, v, t, hit; abi.HIT_DTYPE), or with --any true a bool array.
+Bounded queries (jt_intersect_bounded, jt_occluded_bounded): --tmax X ends every ray at t = X, a hit
+exactly there included, and a rays file of shape (n, 7) carries a per-ray bound in its last column.
+--segments seg.npy, (n, 6) float32 = the two ends of a segment, takes the place of --rays and writes
+a bool array: whether nothing lies between the ends (jt_visible).
+
+    python -m jtrace.query --scene scene.json --rays rays.npy --tmax 2.5 --any true --output shadowed.npy
+    python -m jtrace.query --scene scene.json --segments links.npy --output visible.npy
 The scene, camera, BVH and traversal flags are those of `python -m jtrace` (cli.py); nothing is
 traced. One line is printed: rays, hits, milliseconds of the query call.
 """
@@ -27,7 +34,10 @@ from .trace import make_scene_bvh, make_trace_lights, make_trace_state
 def _parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="jtrace.query", description="ray queries on a scene (jt_intersect, jt_occluded)")
     p.add_argument("--scene", type=str, required=True, help="scene filename")
-    p.add_argument("--rays", type=str, required=True, help=".npy file of rays, (n, 6) float32: origin, direction")
+    src = p.add_mutually_exclusive_group(required=True)
+    src.add_argument("--rays", type=str, help=".npy file of rays, (n, 6) float32: origin, direction; (n, 7): and a bound")
+    src.add_argument("--segments", type=str, help=".npy file of segments, (n, 6) float32: the two ends; writes visible flags")
+    p.add_argument("--tmax", type=float, default=None, help="one bound for all rays: hits up to t = tmax count")
     p.add_argument("--output", type=str, required=True, help=".npy file of the results")
     p.add_argument("--any", type=_bool, default=False, help="any-hit flags (jt_occluded) instead of closest hits")
     p.add_argument("--camera", type=str, default="", help="camera name")
@@ -42,10 +52,21 @@ def _parser() -> argparse.ArgumentParser:
 
 
 def run(ns, out=print) -> dict:
-    rays = np.load(ns.rays)
-    if rays.ndim != 2 or rays.shape[1] != 6:
-        raise SystemExit(f"--rays {ns.rays}: expected shape (n, 6), got {rays.shape}")
-    rays = np.ascontiguousarray(rays, np.float32)
+    segments = ns.rays is None
+    rays = np.load(ns.segments if segments else ns.rays)
+    tmax = ns.tmax
+    if segments:
+        if rays.ndim != 2 or rays.shape[1] != 6:
+            raise SystemExit(f"--segments {ns.segments}: expected shape (n, 6), got {rays.shape}")
+        if tmax is not None or ns.any:
+            raise SystemExit("--segments takes neither --tmax nor --any: a segment is its own bound, the output is visible flags")
+    elif rays.ndim != 2 or rays.shape[1] not in (6, 7):
+        raise SystemExit(f"--rays {ns.rays}: expected shape (n, 6) or (n, 7), got {rays.shape}")
+    elif rays.shape[1] == 7:
+        if tmax is not None:
+            raise SystemExit("--tmax and a bound column in --rays: give one")
+        tmax = np.ascontiguousarray(rays[:, 6], np.float32)
+    rays = np.ascontiguousarray(rays[:, :6], np.float32)
     scene = load_scene(ns.scene, ns.noparallel, missing=ns.missing)
     camera = find_camera(scene, ns.camera)
     lib = abi.load_library()
@@ -57,15 +78,23 @@ def run(ns, out=print) -> dict:
                     traversal=ns.traversal)
     state = make_trace_state(scene_abi, bvh, lights, abi.make_params(params, camera), lib)
     t0 = time.perf_counter()
-    result = state.occluded(rays) if ns.any else state.intersect(rays)
+    if segments:
+        result = state.visible(rays)
+    else:
+        result = state.occluded(rays, tmax=tmax) if ns.any else state.intersect(rays, tmax=tmax)
     ms = (time.perf_counter() - t0) * 1e3
     traversal = state.traversal
     state.close()
     # through a file object: np.save then keeps the name as given (no ".npy" appended)
     with open(ns.output, "wb") as f:
         np.save(f, result)
+    if segments:
+        visible = int(result.sum())
+        out(f"{len(rays)} segments, {visible} visible, {ms:.3f} ms (traversal {traversal})")
+        return {"rays": len(rays), "visible": visible, "ms": ms}
     hits = int(result.sum()) if ns.any else int((result["hit"] != 0).sum())
-    out(f"{len(rays)} rays, {hits} hits, {ms:.3f} ms ({'any hit' if ns.any else 'closest hit'}, traversal {traversal})")
+    out(f"{len(rays)} rays, {hits} hits, {ms:.3f} ms ({'any hit' if ns.any else 'closest hit'}{'' if tmax is None else ', bounded'}, "
+        f"traversal {traversal})")
     return {"rays": len(rays), "hits": hits, "ms": ms}
 
 

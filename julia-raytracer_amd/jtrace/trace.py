@@ -233,13 +233,37 @@ class TraceState:
         torch.cuda.current_stream(dev).synchronize()
         return torch, len(rays)
 
-    def intersect(self, rays, instance=None):
+    def _bounds(self, rays, tmax):
+        """tmax of a bounded query, a scalar or (n,), as what the library reads: a float32 (n,) numpy
+        array for numpy rays, a contiguous float32 tensor on the rays' device for torch rays."""
+        n = len(rays)
+        if hasattr(rays, "data_ptr"):
+            import torch
+            if isinstance(tmax, torch.Tensor):
+                t = tmax.to(device=rays.device, dtype=torch.float32)
+            else:
+                t = torch.as_tensor(np.asarray(tmax, np.float32), device=rays.device)
+            t = t.expand(n).contiguous() if t.dim() == 0 else t.contiguous()
+            torch.cuda.current_stream(rays.device.index).synchronize()
+        else:
+            if hasattr(tmax, "data_ptr"):
+                tmax = tmax.cpu().numpy()
+            t = np.asarray(tmax, np.float32)
+            t = np.full(n, t, np.float32) if t.ndim == 0 else np.ascontiguousarray(t)
+        if tuple(t.shape) != (n,):
+            raise ValueError(f"tmax: expected a scalar or shape ({n},), got {tuple(t.shape)}")
+        return t
+
+    def intersect(self, rays, instance=None, tmax=None):
         """jt_intersect: the closest hit of every ray (n, 6) = (origin, direction) on the context's
         scene, in the context's traversal; instance: None, or per ray -1 (the scene) or an
         instance id (that instance only). A float32 numpy array gives a structured array with
         jt_hit's fields (abi.HIT_DTYPE); a torch tensor on the context's device goes zero-copy
         through jt_intersect_device and gives an int32 (n, 6) tensor of the records (split_hits
-        names the fields)."""
+        names the fields). tmax (a scalar or (n,)): jt_intersect_bounded, the query of the ray
+        that ends at t = tmax, a hit exactly there included; None: unbounded."""
+        if tmax is not None:
+            return self._intersect_bounded(rays, instance, self._bounds(rays, tmax))
         if hasattr(rays, "data_ptr"):
             torch, n = self._device_rays(rays, instance)
             out = torch.empty((n, 6), dtype=torch.int32, device=rays.device)
@@ -260,9 +284,45 @@ class TraceState:
                                                   out.ctypes.data_as(C.POINTER(abi.jt_hit))))
         return out
 
-    def occluded(self, rays):
+    def _intersect_bounded(self, rays, instance, tmax):
+        if hasattr(rays, "data_ptr"):
+            torch, n = self._device_rays(rays, instance)
+            out = torch.empty((n, 6), dtype=torch.int32, device=rays.device)
+            abi.check(self.lib, self.lib.jt_intersect_bounded_device(self.handle, n, rays.data_ptr(), tmax.data_ptr(),
+                                                                     None if instance is None else instance.data_ptr(),
+                                                                     out.data_ptr()))
+            return out
+        rays = _host_rays(rays)
+        n = len(rays)
+        ip = None
+        if instance is not None:
+            instance = np.ascontiguousarray(instance, np.int32)
+            if instance.shape != (n,):
+                raise ValueError(f"instance: expected shape ({n},), got {instance.shape}")
+            ip = instance.ctypes.data_as(abi.i32p)
+        out = np.empty(n, abi.HIT_DTYPE)
+        abi.check(self.lib, self.lib.jt_intersect_bounded(self.handle, n, rays.ctypes.data_as(abi.f32p),
+                                                          tmax.ctypes.data_as(abi.f32p), ip,
+                                                          out.ctypes.data_as(C.POINTER(abi.jt_hit))))
+        return out
+
+    def occluded(self, rays, tmax=None):
         """jt_occluded: bool (n,), whether anything is hit along each ray (a numpy array, or for a
-        torch tensor on the context's device a torch.bool tensor there, zero-copy)."""
+        torch tensor on the context's device a torch.bool tensor there, zero-copy). tmax (a scalar
+        or (n,)): jt_occluded_bounded, anything within t <= tmax; None: unbounded."""
+        if tmax is not None:
+            tmax = self._bounds(rays, tmax)
+            if hasattr(rays, "data_ptr"):
+                torch, n = self._device_rays(rays)
+                out = torch.empty(n, dtype=torch.uint8, device=rays.device)
+                abi.check(self.lib, self.lib.jt_occluded_bounded_device(self.handle, n, rays.data_ptr(), tmax.data_ptr(),
+                                                                        out.data_ptr()))
+                return out != 0
+            rays = _host_rays(rays)
+            out = np.empty(len(rays), np.uint8)
+            abi.check(self.lib, self.lib.jt_occluded_bounded(self.handle, len(rays), rays.ctypes.data_as(abi.f32p),
+                                                             tmax.ctypes.data_as(abi.f32p), out.ctypes.data_as(abi.u8p)))
+            return out != 0
         if hasattr(rays, "data_ptr"):
             torch, n = self._device_rays(rays)
             out = torch.empty(n, dtype=torch.uint8, device=rays.device)
@@ -272,6 +332,22 @@ class TraceState:
         out = np.empty(len(rays), np.uint8)
         abi.check(self.lib, self.lib.jt_occluded(self.handle, len(rays), rays.ctypes.data_as(abi.f32p),
                                                  out.ctypes.data_as(abi.u8p)))
+        return out != 0
+
+    def visible(self, segments):
+        """jt_visible: bool (n,), whether nothing lies between the two ends of each segment (n, 6) =
+        (a, b): 1 - occluded of the ray (a, b - a) bounded by 1 - ray_eps, so a surface through
+        either end does not hide it. numpy gives numpy, a torch tensor on the context's device a
+        torch.bool tensor there."""
+        if hasattr(segments, "data_ptr"):
+            torch, n = self._device_rays(segments)
+            out = torch.empty(n, dtype=torch.uint8, device=segments.device)
+            abi.check(self.lib, self.lib.jt_visible_device(self.handle, n, segments.data_ptr(), out.data_ptr()))
+            return out != 0
+        segments = _host_rays(segments)
+        out = np.empty(len(segments), np.uint8)
+        abi.check(self.lib, self.lib.jt_visible(self.handle, len(segments), segments.ctypes.data_as(abi.f32p),
+                                                out.ctypes.data_as(abi.u8p)))
         return out != 0
 
     # --- the surface at a hit (jt_eval_hits, jt_camera_rays, jt_gbuffer: include/jtrace.h)
@@ -402,6 +478,26 @@ class TraceState:
         out = np.empty((len(points), 6), np.float32)
         abi.check(self.lib, self.lib.jt_hemisphere_rays(self.handle, len(points), points.ctypes.data_as(abi.f32p), int(stream_base),
                                                         int(sample), out.ctypes.data_as(abi.f32p)))
+        return out
+
+    def ambient_occlusion(self, points, radius, sample_begin: int = 0, sample_end: int = 1, stream_base: int = 0):
+        """jt_ambient_occlusion: at every point (n, 6) = (position, normal) the share of samples
+        [sample_begin, sample_end) whose hemisphere_rays ray meets nothing within `radius` (> 0,
+        inf: unbounded): (n,) float32 in [0, 1], 1 fully open. numpy gives numpy; a torch tensor on
+        the context's device goes zero-copy through jt_ambient_occlusion_device and gives a tensor
+        there. One sample s is 1 - occluded(hemisphere_rays(points, s), tmax=radius)."""
+        if hasattr(points, "data_ptr"):
+            torch, n = self._device_rays(points)
+            out = torch.empty(n, dtype=torch.float32, device=points.device)
+            abi.check(self.lib, self.lib.jt_ambient_occlusion_device(self.handle, n, points.data_ptr(), int(stream_base),
+                                                                     int(sample_begin), int(sample_end), float(radius),
+                                                                     out.data_ptr()))
+            return out
+        points = _host_rays(points)
+        out = np.empty(len(points), np.float32)
+        abi.check(self.lib, self.lib.jt_ambient_occlusion(self.handle, len(points), points.ctypes.data_as(abi.f32p), int(stream_base),
+                                                          int(sample_begin), int(sample_end), float(radius),
+                                                          out.ctypes.data_as(abi.f32p)))
         return out
 
     def counters(self) -> dict:
