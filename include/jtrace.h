@@ -329,7 +329,9 @@ int jt_device_count(int32_t* out);
  *                            of a k-way tile split when one process per GPU shards a render by
  *                            tiles (bench.py); jt_create_multi sets its own split instead
  *   "test_lds_ring" "1|2|4|8|16"  (tests only) use that many LDS ring entries, the rest overflow to
- *                            HBM: the overflow path on small scenes */
+ *                            HBM: the overflow path on small scenes
+ *   "test_probe_chunk" "<n>"  (tests only) jt_probe_sh's host variant stages at most n points per
+ *                            chunk instead of 2^22: a chunk boundary on a small array */
 int jt_set_option(const char* name, const char* value);
 
 /* ---- host helpers (CPU only) ------------------------------------------------------- */
@@ -837,6 +839,74 @@ int jt_ambient_occlusion(jt_ctx* ctx, int64_t n, const float* points /* n x (pos
                          int32_t sample_begin, int32_t sample_end, float radius, float* visibility /* n */);
 int jt_ambient_occlusion_device(jt_ctx* ctx, int64_t n, const void* d_points, int64_t stream_base,
                                 int32_t sample_begin, int32_t sample_end, float radius, void* d_visibility);
+
+/* ---- spherical-harmonic radiance probes ---------------------------------------------------- */
+/* What a grid of light probes for dynamic objects needs: at a position, the incoming radiance over
+ * the whole sphere projected onto the nine real spherical harmonics of bands 0..2. jt_irradiance
+ * gathers over a hemisphere and returns a mean that is already cosine-convolved; here every sample
+ * goes along a uniform direction over the sphere and is weighted by the basis at that direction.
+ * A point record is 3 floats, the position.
+ * The ray of (point i, sample s), which jt_sphere_rays writes to rays[6 i ..] and jt_probe_sh
+ * starts sample s with:
+ *   - rng = rng_init(params.seed, stream_base + i, s), as in jt_radiance;
+ *   - ruv = rand2f(rng); the second rand2f is drawn and discarded, so after the prologue the
+ *     stream is exactly where jt_radiance leaves it;
+ *   - o = position, as given (its bits); d = sample_sphere(ruv), which the reference names but
+ *     never defines, so the library's own: z = 2 ruv.y - 1, r = sqrt(clamp(1 - z z, 0, 1)),
+ *     phi = 2 pi ruv.x, d = normalize((r cos phi, r sin phi, z)) in world axes, with the square
+ *     root, sine, cosine and normalize of sample_hemisphere_cos.
+ * The basis, in float32, every operation rounded, no fused multiply-adds, in this association,
+ * with (x, y, z) = d:
+ *   c0 = 0.282095f  c1 = 0.488603f  c2 = 1.092548f  c3 = 0.315392f  c4 = 0.546274f
+ *   Y0 = c0            Y1 = c1*y            Y2 = c1*z            Y3 = c1*x
+ *   Y4 = c2*(x*y)      Y5 = c2*(y*z)        Y6 = c3*(3.0f*(z*z) - 1.0f)
+ *   Y7 = c2*(x*z)      Y8 = c4*(x*x - y*y)
+ * jt_probe_sh: for every point i the running mean over samples [sample_begin, sample_end), in
+ * order, of target * Y_k. For sample s, target is exactly jt_radiance's rgba target on the ray
+ * above: the path state, the context's sampler, bounces, nocaustics, envhidden, clamp and
+ * traversal, then trace_sample's epilogue, (radiance, 1) or (0, 0, 0, 0). For k = 0..8 and each of
+ * the four channels c:
+ *   v = target.c * Y_k;  acc_k.c = acc_k.c * (1 - w) + v * w,  w = 1 / (float)(s - sample_begin + 1)
+ * with acc from 0 and the weight as the integrator computes it. sh[(9 i + k) * 4 + c] = acc_k.c
+ * after the last sample: nine rgba coefficients per point, 144 bytes.
+ * The first step of the fold is 0 * 0 + v * 1, so a product of -0 (zero radiance times a negative
+ * Y_k) becomes +0: a one-sample call is that step, not the bare product, and no result of the
+ * call holds a -0 that came from a zero target.
+ * The contract: jt_probe_sh(points, base, s, s + 1) is, in every bit, that fold step applied to
+ * jt_radiance(jt_sphere_rays(points, base, s), base, s, s + 1) and Y(d) of those rays, and a range
+ * is the float32 fold above of its one-sample results. A point's result depends on the point, its
+ * stream and the sample range only: an array split over several calls, stream_base advanced by the
+ * points already done, gives the bits of one call.
+ * What the coefficients are: the directions have the pdf 1 / (4 pi), so the radiance field's SH
+ * coefficients are L_k = 4 pi * sh_k.rgb, and the irradiance about a unit normal n is
+ * E(n) = sum_k A_l(k) L_k Y_k(n) with A = pi, 2 pi / 3, pi / 4 for bands 0, 1, 2. The alpha channel
+ * is the same projection of the coverage flag: in a scene without an environment, or with
+ * envhidden, c0 - sh_0.a and the higher -sh_k.a are the SH of sky visibility. Coefficient 0 over c0
+ * is the plain mean over the sphere.
+ * Everything else as jt_radiance: the calls read the scene and the parameters only (image, AOVs,
+ * stream means, variance, the adaptive mask and every jt_counters field stay bit for bit as they
+ * were, queued samples stay queued); the *_device variants take device pointers on the context's
+ * device (d_sh aligned to 16 bytes, d_rays to 8), run on the context's stream and return when it
+ * is idle. The host variant of jt_sphere_rays stages through the buffers the ray queries' host
+ * variants use; jt_probe_sh's runs the array in chunks of at most 2^22 points through a staging
+ * buffer of its own, stream_base advanced, which by the contract gives the bits of one call.
+ * rays must not overlap points: the records differ in size.
+ * Errors, in jt_radiance's order: JT_ERR_INVALID (naming the argument) for a NULL ctx, points or
+ * output, n < 0 or n > 2^30, stream_base < 0 or stream_base + n > 2^31, then for jt_probe_sh
+ * sample_begin < 0, sample_end <= sample_begin, more than 2^24 samples, for jt_sphere_rays
+ * sample < 0, then a d_sh not aligned to 16 bytes or a d_rays not aligned to 8, before the context
+ * is looked at and before anything is written; n == 0 returns JT_OK with no device work;
+ * JT_ERR_UNSUPPORTED for a multi-device context; JT_ERR_STATE for a failed context.
+ * A non-finite position is the caller's responsibility: every lane still ends in a bounded number
+ * of steps, the result for such a point is unspecified. */
+int jt_probe_sh(jt_ctx* ctx, int64_t n, const float* points /* n x 3 */, int64_t stream_base,
+                int32_t sample_begin, int32_t sample_end, float* sh /* n x 9 x 4 */);
+int jt_probe_sh_device(jt_ctx* ctx, int64_t n, const void* d_points, int64_t stream_base,
+                       int32_t sample_begin, int32_t sample_end, void* d_sh);
+int jt_sphere_rays(jt_ctx* ctx, int64_t n, const float* points /* n x 3 */, int64_t stream_base, int32_t sample,
+                   float* rays /* n x 6 */);
+int jt_sphere_rays_device(jt_ctx* ctx, int64_t n, const void* d_points, int64_t stream_base, int32_t sample,
+                          void* d_rays);
 
 /* zero accumulators (at once if their device pointers were handed out, else before they are
  * next read or overwritten), samples = 0, queued samples dropped */

@@ -81,6 +81,17 @@ __device__ __forceinline__ v3 sample_hemisphere_cos(v3 normal, v2 ruv) {
     v3 local = V3(r * c, r * s, z);
     return normalize(mul(basis_fromz(normal), local));
 }
+// The uniform draw over the whole sphere, in world axes (pdf 1 / 4 pi). The reference calls a
+// sample_sphere it never defines (which is why jt_create rejects untextured environments); this is
+// Yocto's, with the square root, sine, cosine and normalize that sample_hemisphere_cos uses.
+__device__ __forceinline__ v3 sample_sphere(v2 ruv) {
+    float z = 2 * ruv.y - 1;
+    float r = __builtin_sqrtf(jl_clamp(1 - z * z, 0.0f, 1.0f));
+    float phi = 2 * pif * ruv.x;
+    float s, c;
+    jl_sincos(phi, &s, &c);
+    return normalize(V3(r * c, r * s, z));
+}
 // GGX microfacet_distribution / shadowing / sampling (src/shading.jl:734-816)
 __device__ __forceinline__ float microfacet_distribution(float roughness, v3 normal, v3 halfway) {
     float cosine = dot(normal, halfway);

@@ -107,16 +107,20 @@ struct jt_ctx {
     // buffers and their jt_surface records in Q_SURF (q_stage_surf records); jt_radiance
     // (jt_radiance.hip) launches on the same counter and overflow area and stages its rays in
     // Q_RAYS and its means in Q_OUT; the bounded queries (jt_intersect_bounded, jt_occluded_bounded)
-    // stage their per-ray bounds in Q_TMAX, grown with the rays
+    // stage their per-ray bounds in Q_TMAX, grown with the rays; jt_probe_sh's host variant stages a
+    // chunk's 144-byte records in Q_SH (q_stage_sh records; at most probe_chunk points a chunk,
+    // jtr::PROBE_MAX_CHUNK unless the option test_probe_chunk lowers it)
     std::vector<int> inst_new;
     int* q_to_dev = nullptr;
     int* q_to_ref = nullptr;
     unsigned* q_counter = nullptr;
-    enum { Q_OVF = 0, Q_RAYS, Q_INST, Q_OUT, Q_SURF, Q_TMAX, Q_NGROW };
-    void* q_grow[Q_NGROW] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    enum { Q_OVF = 0, Q_RAYS, Q_INST, Q_OUT, Q_SURF, Q_TMAX, Q_SH, Q_NGROW };
+    void* q_grow[Q_NGROW] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     size_t q_ovf_entries = 0;
     long long q_stage_rays = 0;
     long long q_stage_surf = 0;
+    long long q_stage_sh = 0;
+    long long probe_chunk = (long long)1 << 22;
     // inst_nelem: the elements of each instance's shape, in the caller's numbering (jt_create);
     // uploaded by the first surface call (s_nelem, in `allocations`): surface_kernel's range check
     std::vector<int> inst_nelem;

@@ -33,6 +33,13 @@ constexpr size_t RADIANCE_LDS_BYTES = (size_t)(jtq::QUERY_RING + RADIANCE_SLOTS)
 #define JT_RADIANCE_NODE_REPEAT 3
 #endif
 constexpr int RADIANCE_NODE_REPEAT = JT_RADIANCE_NODE_REPEAT;
+// Where jt_probe_sh's 36 running sums live (EXPERIMENTS.md, "The sphere source and the SH
+// projection"): 0, the lane's own output record in HBM, read and written per finished sample; 1
+// (an A/B build), 36 more LDS slots per lane, which takes the workgroup from 31 744 to 68 608 B
+// and the CU from three workgroups to two.
+#ifndef JT_PROBE_LDS
+#define JT_PROBE_LDS 0
+#endif
 
 // The step kind of a wave's iteration, from the lanes that want each: np a primitive test, nn a
 // node step, ns a shading step (their query is done). Traversal steps are picked by the ray
@@ -54,7 +61,18 @@ constexpr int radiance_step(int np, int nn, int ns) {
 // Where a sample's ray comes from (radiance_kernel's SOURCE): the caller's ray record as it stands
 // (jt_radiance), or the caller's point record (position, normal) and a cosine-weighted direction
 // about the normal drawn from the sample's own stream (jt_irradiance, jt_hemisphere_rays)
-enum : int { SOURCE_RAY = 0, SOURCE_HEMISPHERE = 1 };
+enum : int { SOURCE_RAY = 0, SOURCE_HEMISPHERE = 1, SOURCE_SPHERE = 2 };
+// SOURCE_SPHERE: the caller's record is a position alone and the direction a uniform draw over the
+// whole sphere from the sample's stream (jt_probe_sh, jt_sphere_rays). The floats of a source's
+// record, a compile-time property of the source: whoever reads record i reads it at this stride.
+constexpr int source_stride(int source) { return source == SOURCE_SPHERE ? 3 : 6; }
+
+// jt_probe_sh's host variant runs the caller's array in chunks of at most this many points, each
+// staged and copied out on its own (a probe's record is 144 bytes): stream_base advances with the
+// chunks, which the contract makes bit-identical to one call. The option test_probe_chunk (tests
+// only) lowers it.
+constexpr int64_t PROBE_MAX_CHUNK = (int64_t)1 << 22;
+constexpr int64_t probe_chunk(int64_t option) { return option >= 1 && option < PROBE_MAX_CHUNK ? option : PROBE_MAX_CHUNK; }
 
 // the argument rules of jt_radiance that do not need the context, in the header's order; nullptr:
 // all hold, else the message

@@ -1,7 +1,9 @@
 // jt_radiance.hip — the path integrator on the caller's own rays (include/jtrace.h: jt_radiance and
 // its device-pointer variant; DESIGN.md §6g "Radiance along the caller's rays") and at the caller's
 // own points, every sample along a cosine-weighted direction of its own (jt_irradiance,
-// jt_hemisphere_rays and their device-pointer variants): the megakernel's
+// jt_hemisphere_rays and their device-pointer variants), or along a uniform direction
+// over the whole sphere with every sample projected onto nine spherical harmonics (jt_probe_sh,
+// jt_sphere_rays and their device-pointer variants; jt_sh.h): the megakernel's
 // integrator (jt_integrator.h: Path, path_hit, naive_hit, light_hit) driven by the ray queries'
 // persistent, refilling grid instead of the megakernel's pixel hand-out: query_kernel's refill itself
 // (feed_refill, jt_feed.h), its grid, claim size, ray counter and scene (jt_intersect.h; query_setup,
@@ -15,7 +17,9 @@
 // running mean, its sample index and the parked path state (Path::pk) live in the lane's LDS slots
 // (jt_radiance.h), the stack ring beside them. Where a sample's ray comes from is the kernel's
 // compile-time SOURCE (radiance_ray, jt_sample_ray.h): the record as it stands, or the hemisphere draw about the
-// record's normal; nothing else differs, and hemisphere_kernel writes that same ray out.
+// record's normal; nothing else differs, and hemisphere_kernel writes that same ray out. The third
+// source, the sphere draw at the record's position (sphere_kernel writes it out), also changes where
+// the mean lives: a probe's 36 running sums are its own output record, not LDS slots.
 //
 // Each iteration of a wave runs one step kind, chosen by a lane vote (radiance_step):
 //   a primitive step   prim_step
@@ -44,14 +48,15 @@
 #include "jt_integrator.h"
 #include "jt_radiance.h"
 #include "jt_sample_ray.h"
+#include "jt_sh.h"
 
 namespace jtk {
 
 using jtq::QUERY_RING;
 
 struct DRadiance {
-    const float* rays;      // n x (o, d); SOURCE_HEMISPHERE: n x (position, normal)
-    float4* rgba;           // n means
+    const float* rays;      // n x (o, d); SOURCE_HEMISPHERE: n x (position, normal); SOURCE_SPHERE: n x position
+    float4* rgba;           // n means; SOURCE_SPHERE: n probes of nine float4 (jt_sh.h)
     long long stream_base;  // ray i draws from stream stream_base + i
     int s_begin, s_end;     // the samples of every ray, in order
     DFeed feed;             // the n rays' hand-out
@@ -105,10 +110,12 @@ __global__ __launch_bounds__(BLOCK) JT_RADIANCE_WAVES_ATTR void radiance_kernel(
     // ---- refill (jt_feed.h): a lane without a ray takes one of the wave's reserve and starts its first sample
     while (feed_refill(Q.feed, reserve, ray >= 0, [&](int r) {
         ray = r;
-        acc[0] = 0.0f;
-        acc[BLOCK] = 0.0f;
-        acc[2 * BLOCK] = 0.0f;
-        acc[3 * BLOCK] = 0.0f;
+        if constexpr (SOURCE != jtr::SOURCE_SPHERE) {  // a probe's sums live in its output record
+            acc[0] = 0.0f;
+            acc[BLOCK] = 0.0f;
+            acc[2 * BLOCK] = 0.0f;
+            acc[3 * BLOCK] = 0.0f;
+        }
         *cur = Q.s_begin;
         radiance_start<F, SOURCE>(P, Q, ray, Q.s_begin, st);
         query_start<WIDE>(S, T, st.o, st.d, -1, stack);
@@ -147,12 +154,61 @@ __global__ __launch_bounds__(BLOCK) JT_RADIANCE_WAVES_ATTR void radiance_kernel(
                 const bool hit = st.flag(F_HIT);
                 const bool env = !hit && !P.envhidden && S.nenvs != 0;
                 const v4 target = (hit || env) ? V4(radiance.x, radiance.y, radiance.z, 1) : V4(0, 0, 0, 0);
-                acc[0] = acc[0] * omw + target.x * w;
-                acc[BLOCK] = acc[BLOCK] * omw + target.y * w;
-                acc[2 * BLOCK] = acc[2 * BLOCK] * omw + target.z * w;
-                acc[3 * BLOCK] = acc[3 * BLOCK] * omw + target.w * w;
+                if constexpr (SOURCE == jtr::SOURCE_SPHERE) {
+                    // The projection (jt_sh.h): the 36 running sums are the lane's own output record,
+                    // nine float4 at rgba + 9 ray, which no other lane touches; a read-modify-write
+                    // with plain vector loads and stores. The first sample folds from zero without
+                    // reading the record (and turns a product of -0 into +0). The sample's initial
+                    // direction is drawn again by the arm that started it: the same function, the
+                    // same bits, and nothing parked across the path.
+                    Rng rng0;
+                    v3 o0, d0;
+                    radiance_ray<SOURCE>(P, Q.rays, Q.stream_base, ray, sample, rng0, o0, d0);
+                    const jtsh::Basis Y = jtsh::sh_basis(d0.x, d0.y, d0.z);
+                    float4* const rec = Q.rgba + (size_t)ray * jtsh::SH_COEFFS;
+                    const bool first = sample == Q.s_begin;
+#if JT_PROBE_LDS
+                    // A/B build (EXPERIMENTS.md): the sums in 36 more LDS slots per lane, 36 KiB per
+                    // workgroup (two workgroups per CU instead of three), the record written once
+                    __shared__ float sums[jtsh::SH_RECORD * BLOCK];
+                    float* const mine = sums + threadIdx.x;
+                    const bool last = sample + 1 >= Q.s_end;
+#pragma unroll
+                    for (int k = 0; k < jtsh::SH_COEFFS; k++) {
+                        float* const m = mine + 4 * k * BLOCK;
+                        float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                        if (!first) a = make_float4(m[0], m[BLOCK], m[2 * BLOCK], m[3 * BLOCK]);
+                        a.x = jtsh::sh_fold(a.x, target.x, Y.y[k], w, omw);
+                        a.y = jtsh::sh_fold(a.y, target.y, Y.y[k], w, omw);
+                        a.z = jtsh::sh_fold(a.z, target.z, Y.y[k], w, omw);
+                        a.w = jtsh::sh_fold(a.w, target.w, Y.y[k], w, omw);
+                        m[0] = a.x;
+                        m[BLOCK] = a.y;
+                        m[2 * BLOCK] = a.z;
+                        m[3 * BLOCK] = a.w;
+                        if (last) rec[k] = a;
+                    }
+#else
+#pragma unroll
+                    for (int k = 0; k < jtsh::SH_COEFFS; k++) {
+                        float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                        if (!first) a = rec[k];
+                        a.x = jtsh::sh_fold(a.x, target.x, Y.y[k], w, omw);
+                        a.y = jtsh::sh_fold(a.y, target.y, Y.y[k], w, omw);
+                        a.z = jtsh::sh_fold(a.z, target.z, Y.y[k], w, omw);
+                        a.w = jtsh::sh_fold(a.w, target.w, Y.y[k], w, omw);
+                        rec[k] = a;
+                    }
+#endif
+                } else {
+                    acc[0] = acc[0] * omw + target.x * w;
+                    acc[BLOCK] = acc[BLOCK] * omw + target.y * w;
+                    acc[2 * BLOCK] = acc[2 * BLOCK] * omw + target.z * w;
+                    acc[3 * BLOCK] = acc[3 * BLOCK] * omw + target.w * w;
+                }
                 if (sample + 1 >= Q.s_end) {
-                    Q.rgba[ray] = make_float4(acc[0], acc[BLOCK], acc[2 * BLOCK], acc[3 * BLOCK]);
+                    if constexpr (SOURCE != jtr::SOURCE_SPHERE)
+                        Q.rgba[ray] = make_float4(acc[0], acc[BLOCK], acc[2 * BLOCK], acc[3 * BLOCK]);
                     ray = -1;
                 } else {
                     *cur = sample + 1;
@@ -174,6 +230,21 @@ __global__ __launch_bounds__(BLOCK) void hemisphere_kernel(DParams P, const floa
     Rng rng;
     v3 o, d;
     radiance_ray<jtr::SOURCE_HEMISPHERE>(P, points, stream_base, i, sample, rng, o, d);
+    float2* const y = rays + (size_t)i * 3;
+    y[0] = make_float2(o.x, o.y);
+    y[1] = make_float2(o.z, d.x);
+    y[2] = make_float2(d.y, d.z);
+}
+
+// jt_sphere_rays: the same for radiance_kernel<.., SOURCE_SPHERE>, whose record is a position alone
+// (3 floats in, 6 out: rays must not be the points' own array)
+__global__ __launch_bounds__(BLOCK) void sphere_kernel(DParams P, const float* points, long long stream_base, int sample, int n,
+                                                       float2* rays) {
+    const int i = (int)blockIdx.x * BLOCK + (int)threadIdx.x;  // n <= 2^30 (QUERY_MAX_RAYS)
+    if (i >= n) return;
+    Rng rng;
+    v3 o, d;
+    radiance_ray<jtr::SOURCE_SPHERE>(P, points, stream_base, i, sample, rng, o, d);
     float2* const y = rays + (size_t)i * 3;
     y[0] = make_float2(o.x, o.y);
     y[1] = make_float2(o.z, d.x);
@@ -210,8 +281,27 @@ int hemisphere_check(const jt_ctx* c, int64_t n, const void* points, const char*
                           device && ((uintptr_t)out & 7) ? "d_rays must be aligned to 8 bytes" : nullptr, RADIANCE_MULTI, n == 0, done);
 }
 
-// n >= 1 records (SOURCE_RAY: rays, SOURCE_HEMISPHERE: points) from device pointers, on the context's
-// stream; returns once the stream is idle
+// jt_probe_sh's and jt_sphere_rays': the same rules in the same order, the messages their own
+constexpr const char* PROBE_MULTI =
+    "jt_probe_sh and jt_sphere_rays are not available on a multi-device context (jt_create_multi): use one context per device";
+
+int probe_check(const jt_ctx* c, int64_t n, const void* points, const char* points_name, int64_t stream_base, int32_t s0, int32_t s1,
+                const void* out, const char* out_name, bool device, bool* done) {
+    return ray_call_check(c, {{points, points_name}, {out, out_name}}, jtr::radiance_range_error(n, stream_base, s0, s1),
+                          device && ((uintptr_t)out & 15) ? "d_sh must be aligned to 16 bytes" : nullptr, PROBE_MULTI, n == 0, done);
+}
+
+int sphere_check(const jt_ctx* c, int64_t n, const void* points, const char* points_name, int64_t stream_base, int32_t sample,
+                 const void* out, const char* out_name, bool device, bool* done) {
+    const char* range = jtr::radiance_range_error(n, stream_base, 0, 1);
+    if (!range && sample < 0) range = "sample must be at least 0 (jt_sphere_rays)";
+    return ray_call_check(c, {{points, points_name}, {out, out_name}}, range,
+                          device && ((uintptr_t)out & 7) ? "d_rays must be aligned to 8 bytes (jt_sphere_rays)" : nullptr, PROBE_MULTI,
+                          n == 0, done);
+}
+
+// n >= 1 records (SOURCE_RAY: rays, SOURCE_HEMISPHERE: points, SOURCE_SPHERE: positions, d_rgba then
+// the probes' records) from device pointers, on the context's stream; returns once the stream is idle
 template <int SOURCE>
 int radiance_run(jt_ctx* c, int64_t n, const void* d_recs, int64_t stream_base, int32_t s0, int32_t s1, void* d_rgba) {
     (void)hipSetDevice(c->device);
@@ -234,7 +324,9 @@ int radiance_run(jt_ctx* c, int64_t n, const void* d_recs, int64_t stream_base, 
         hipLaunchKernelGGL((jtk::radiance_kernel<wide(), over(), naive() ? 2 : 1, SOURCE>), dim3((unsigned)grid), dim3(BLOCK), 0, c->stream,
                            S, c->P, Q);
     });
-    return launch_finish(c, SOURCE == jtr::SOURCE_RAY ? "radiance kernel" : "irradiance kernel");
+    return launch_finish(c, SOURCE == jtr::SOURCE_RAY          ? "radiance kernel"
+                            : SOURCE == jtr::SOURCE_HEMISPHERE ? "irradiance kernel"
+                                                               : "probe kernel");
 }
 
 // the host variants of both: the records staged in Q_RAYS, the means in Q_OUT, whose jt_hit slot
@@ -259,6 +351,42 @@ int hemisphere_run(jt_ctx* c, int64_t n, const void* d_points, int64_t stream_ba
     hipLaunchKernelGGL(jtk::hemisphere_kernel, dim3(grid), dim3(BLOCK), 0, c->stream, c->P, (const float*)d_points, (long long)stream_base,
                        (int)sample, (int)n, (float2*)d_rays);
     return launch_finish(c, "hemisphere kernel");
+}
+
+int sphere_run(jt_ctx* c, int64_t n, const void* d_points, int64_t stream_base, int32_t sample, void* d_rays) {
+    (void)hipSetDevice(c->device);
+    const unsigned grid = (unsigned)((n + BLOCK - 1) / BLOCK);
+    hipLaunchKernelGGL(jtk::sphere_kernel, dim3(grid), dim3(BLOCK), 0, c->stream, c->P, (const float*)d_points, (long long)stream_base,
+                       (int)sample, (int)n, (float2*)d_rays);
+    return launch_finish(c, "sphere kernel");
+}
+
+// jt_probe_sh's host variant: chunks of at most c->probe_chunk points, the positions staged in
+// Q_RAYS (a 12-byte record in a 24-byte slot), the records in Q_SH, grown to the chunk; a chunk's
+// streams start where the last one's ended, which gives the bits of one call. (A template like
+// radiance_host, so the kernel's SOURCE_SPHERE instances follow the others in the object.)
+template <int SOURCE>
+int probe_host(jt_ctx* c, int64_t n, const float* points, int64_t stream_base, int32_t s0, int32_t s1, float* sh) {
+    (void)hipSetDevice(c->device);
+    const int64_t chunk = n < c->probe_chunk ? n : c->probe_chunk;
+    int st;
+    if ((st = query_stage(c, chunk))) return st;
+    if (chunk > c->q_stage_sh) {
+        const size_t cap = (size_t)jtq::query_stage_rays(c->q_stage_sh, chunk);
+        c->q_stage_sh = 0;
+        if ((st = query_grow(c, jt_ctx::Q_SH, cap * jtsh::SH_RECORD * sizeof(float), "probe records"))) return st;
+        c->q_stage_sh = (long long)cap;
+    }
+    void* const d_points = c->q_grow[jt_ctx::Q_RAYS];
+    void* const d_sh = c->q_grow[jt_ctx::Q_SH];
+    for (int64_t at = 0; at < n; at += chunk) {
+        const size_t m = (size_t)(n - at < chunk ? n - at : chunk);
+        if ((st = copy_in(d_points, points + (size_t)at * 3, m * 3 * sizeof(float), "hipMemcpy probe points")) ||
+            (st = radiance_run<SOURCE>(c, (int64_t)m, d_points, stream_base + at, s0, s1, d_sh)) ||
+            (st = copy_out(sh + (size_t)at * jtsh::SH_RECORD, d_sh, m * jtsh::SH_RECORD * sizeof(float), "hipMemcpy probe records")))
+            return st;
+    }
+    return JT_OK;
 }
 
 }  // namespace
@@ -320,6 +448,41 @@ int jt_hemisphere_rays(jt_ctx* c, int64_t n, const float* points, int64_t stream
         (st = hemisphere_run(c, n, d_points, stream_base, sample, d_rays)))
         return st;
     return copy_out(rays, d_rays, bytes, "hipMemcpy hemisphere rays");
+}
+
+int jt_probe_sh_device(jt_ctx* c, int64_t n, const void* d_points, int64_t stream_base, int32_t sample_begin, int32_t sample_end,
+                       void* d_sh) {
+    bool done;
+    if (const int st = probe_check(c, n, d_points, "d_points", stream_base, sample_begin, sample_end, d_sh, "d_sh", true, &done)) return st;
+    return done ? JT_OK : radiance_run<jtr::SOURCE_SPHERE>(c, n, d_points, stream_base, sample_begin, sample_end, d_sh);
+}
+
+int jt_probe_sh(jt_ctx* c, int64_t n, const float* points, int64_t stream_base, int32_t sample_begin, int32_t sample_end, float* sh) {
+    bool done;
+    if (const int st = probe_check(c, n, points, "points", stream_base, sample_begin, sample_end, sh, "sh", false, &done)) return st;
+    return done ? JT_OK : probe_host<jtr::SOURCE_SPHERE>(c, n, points, stream_base, sample_begin, sample_end, sh);
+}
+
+int jt_sphere_rays_device(jt_ctx* c, int64_t n, const void* d_points, int64_t stream_base, int32_t sample, void* d_rays) {
+    bool done;
+    if (const int st = sphere_check(c, n, d_points, "d_points", stream_base, sample, d_rays, "d_rays", true, &done)) return st;
+    return done ? JT_OK : sphere_run(c, n, d_points, stream_base, sample, d_rays);
+}
+
+int jt_sphere_rays(jt_ctx* c, int64_t n, const float* points, int64_t stream_base, int32_t sample, float* rays) {
+    bool done;
+    if (const int st = sphere_check(c, n, points, "points", stream_base, sample, rays, "rays", false, &done)) return st;
+    if (done) return JT_OK;
+    (void)hipSetDevice(c->device);
+    // the positions staged in Q_RAYS (12 bytes in a 24-byte slot), the rays in Q_OUT as jt_hemisphere_rays'
+    int st;
+    if ((st = query_stage(c, n))) return st;
+    void* const d_points = c->q_grow[jt_ctx::Q_RAYS];
+    void* const d_rays = c->q_grow[jt_ctx::Q_OUT];
+    if ((st = copy_in(d_points, points, (size_t)n * 3 * sizeof(float), "hipMemcpy sphere points")) ||
+        (st = sphere_run(c, n, d_points, stream_base, sample, d_rays)))
+        return st;
+    return copy_out(rays, d_rays, (size_t)n * 6 * sizeof(float), "hipMemcpy sphere rays");
 }
 
 }  // extern "C"

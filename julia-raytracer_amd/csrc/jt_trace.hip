@@ -23,6 +23,7 @@
 #include "jt_accum.h"
 #include "jt_context.h"
 #include "jt_layout.h"
+#include "jt_radiance.h"
 
 using namespace jtd;
 using namespace jtk;
@@ -321,6 +322,8 @@ int jt_create(const jt_scene* scene, const jt_scene_bvh* bvh, const jt_lights* l
         const jt_shape& sh = scene->shapes[scene->instances[k].shape];
         c->inst_nelem[(size_t)k] = sh.ntriangles ? sh.ntriangles : sh.nquads;  // flatten_shape's kind
     }
+    // option test_probe_chunk (tests only): the points of a chunk of jt_probe_sh's host variant
+    if (const char* pc = jt::opt(opts, "test_probe_chunk")) c->probe_chunk = jtr::probe_chunk(std::atoll(pc));
     auto bail = [&](int status) {
         jt_destroy(c);
         return status;

@@ -351,6 +351,10 @@ def _declare(lib):
     lib.jt_ambient_occlusion.argtypes = [C.c_void_p, C.c_int64, f32p, C.c_int64, C.c_int32, C.c_int32, C.c_float, f32p]
     lib.jt_ambient_occlusion_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_float,
                                                 C.c_void_p]
+    lib.jt_probe_sh.argtypes = [C.c_void_p, C.c_int64, f32p, C.c_int64, C.c_int32, C.c_int32, f32p]
+    lib.jt_probe_sh_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]
+    lib.jt_sphere_rays.argtypes = [C.c_void_p, C.c_int64, f32p, C.c_int64, C.c_int32, f32p]
+    lib.jt_sphere_rays_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
     lib.jt_reset.argtypes = [C.c_void_p]
     lib.jt_get_device_buffers.argtypes = [C.c_void_p, C.POINTER(jt_device_buffers)]
     lib.jt_set_counters.argtypes = [C.c_void_p, C.c_int32]
@@ -376,6 +380,7 @@ EXPORTED_SYMBOLS = [
     "jt_intersect_bounded", "jt_occluded_bounded", "jt_visible",
     "jt_intersect_bounded_device", "jt_occluded_bounded_device", "jt_visible_device",
     "jt_ambient_occlusion", "jt_ambient_occlusion_device",
+    "jt_probe_sh", "jt_probe_sh_device", "jt_sphere_rays", "jt_sphere_rays_device",
 ]
 
 

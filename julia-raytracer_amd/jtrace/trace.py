@@ -500,6 +500,55 @@ class TraceState:
                                                           out.ctypes.data_as(abi.f32p)))
         return out
 
+    # --- spherical-harmonic radiance probes (jt_probe_sh, jt_sphere_rays: include/jtrace.h)
+    def _device_points(self, points):
+        """A torch tensor of (n, 3) positions checked for the zero-copy path: (torch, n)."""
+        import torch
+        dev = int(self.params.device)
+        if self.devices is not None:
+            raise abi.JTError(-2, "probes are not available on a multi-device context")
+        if not (isinstance(points, torch.Tensor) and points.is_cuda and points.device.index == dev and points.dtype == torch.float32
+                and tuple(points.shape) == (len(points), 3) and points.is_contiguous()):
+            raise ValueError(f"points: expected a contiguous torch.float32 tensor of shape ({len(points)}, 3) on cuda:{dev}")
+        torch.cuda.current_stream(dev).synchronize()
+        return torch, len(points)
+
+    def probe_sh(self, points, sample_begin: int = 0, sample_end: int = 1, stream_base: int = 0):
+        """jt_probe_sh: at every point (n, 3) the running mean over samples [sample_begin,
+        sample_end) of the integrator's rgba target along a uniform direction over the sphere, times
+        the nine real spherical harmonics of bands 0..2 at that direction: (n, 9, 4) float32.
+        jtrace.sh turns it into radiance coefficients (4 pi rgb) and irradiance. numpy gives numpy;
+        a torch tensor on the context's device goes zero-copy through jt_probe_sh_device and gives a
+        tensor there. One sample s is the fold step 0 * 0 + (radiance(sphere_rays(points, s), s,
+        s + 1) * sh_basis(d)) * 1 in every bit."""
+        if hasattr(points, "data_ptr"):
+            torch, n = self._device_points(points)
+            out = torch.empty((n, 9, 4), dtype=torch.float32, device=points.device)
+            abi.check(self.lib, self.lib.jt_probe_sh_device(self.handle, n, points.data_ptr(), int(stream_base),
+                                                            int(sample_begin), int(sample_end), out.data_ptr()))
+            return out
+        points = _host_points(points)
+        out = np.empty((len(points), 9, 4), np.float32)
+        abi.check(self.lib, self.lib.jt_probe_sh(self.handle, len(points), points.ctypes.data_as(abi.f32p), int(stream_base),
+                                                 int(sample_begin), int(sample_end), out.ctypes.data_as(abi.f32p)))
+        return out
+
+    def sphere_rays(self, points, sample: int, stream_base: int = 0):
+        """jt_sphere_rays: the (n, 6) float32 rays (origin, direction) probe_sh starts sample
+        `sample` of every point (n, 3) with: the position's bits and the uniform direction over the
+        sphere. numpy gives numpy, a torch tensor on the context's device a tensor there."""
+        if hasattr(points, "data_ptr"):
+            torch, n = self._device_points(points)
+            out = torch.empty((n, 6), dtype=torch.float32, device=points.device)
+            abi.check(self.lib, self.lib.jt_sphere_rays_device(self.handle, n, points.data_ptr(), int(stream_base), int(sample),
+                                                               out.data_ptr()))
+            return out
+        points = _host_points(points)
+        out = np.empty((len(points), 6), np.float32)
+        abi.check(self.lib, self.lib.jt_sphere_rays(self.handle, len(points), points.ctypes.data_as(abi.f32p), int(stream_base),
+                                                    int(sample), out.ctypes.data_as(abi.f32p)))
+        return out
+
     def counters(self) -> dict:
         c = abi.jt_counters()
         abi.check(self.lib, self.lib.jt_get_counters(self.handle, C.byref(c)))
@@ -560,6 +609,13 @@ def _host_rays(rays) -> np.ndarray:
     if rays.ndim != 2 or rays.shape[1] != 6:
         raise ValueError(f"rays: expected shape (n, 6) = (origin, direction), got {rays.shape}")
     return rays
+
+
+def _host_points(points) -> np.ndarray:
+    points = np.ascontiguousarray(points, np.float32)
+    if points.ndim != 2 or points.shape[1] != 3:
+        raise ValueError(f"points: expected shape (n, 3) = position, got {points.shape}")
+    return points
 
 
 def split_hits(records) -> dict:
