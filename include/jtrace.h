@@ -27,7 +27,9 @@
  *                      caller's own rays on the context's scene; jt_occluded its find_any form;
  *                      jt_intersect_bounded, jt_occluded_bounded the same of Ray3f(o, d, ray_eps, tmax),
  *                      jt_visible of a segment; jt_ambient_occlusion the share of a point's
- *                      hemisphere draws that meet nothing within a radius
+ *                      hemisphere draws that meet nothing within a radius;
+ *                      jt_intersect_multi the k nearest hits of that bounded query in one traversal,
+ *                      jt_count_hits how many there are
  *   jt_eval_hits       ~ eval_shading_position / eval_shading_normal / eval_material (src/scene.jl:416-673)
  *                      at the caller's hit records; jt_camera_rays ~ sample_camera (src/trace.jl:651-674);
  *                      jt_gbuffer the two around jt_intersect: the surface under every pixel
@@ -331,7 +333,9 @@ int jt_device_count(int32_t* out);
  *   "test_lds_ring" "1|2|4|8|16"  (tests only) use that many LDS ring entries, the rest overflow to
  *                            HBM: the overflow path on small scenes
  *   "test_probe_chunk" "<n>"  (tests only) jt_probe_sh's host variant stages at most n points per
- *                            chunk instead of 2^22: a chunk boundary on a small array */
+ *                            chunk instead of 2^22: a chunk boundary on a small array
+ *   "test_multi_chunk" "<n>"  (tests only) jt_intersect_multi's host variant stages at most n rays
+ *                            per chunk instead of 2^22 / k */
 int jt_set_option(const char* name, const char* value);
 
 /* ---- host helpers (CPU only) ------------------------------------------------------- */
@@ -642,6 +646,54 @@ int jt_visible(jt_ctx* ctx, int64_t n, const float* segments /* n x (a, b), 6 fl
 int jt_intersect_bounded_device(jt_ctx* ctx, int64_t n, const void* d_rays, const void* d_tmax, const void* d_instance, void* d_hits);
 int jt_occluded_bounded_device(jt_ctx* ctx, int64_t n, const void* d_rays, const void* d_tmax, void* d_occluded);
 int jt_visible_device(jt_ctx* ctx, int64_t n, const void* d_segments, void* d_visible);
+
+/* ---- all hits along a ray ------------------------------------------------------------------ */
+/* The hits behind the first one, in one traversal: transparency and cutout layers, thickness,
+ * inside / outside by crossing parity, and the records jt_eval_hits needs for an opacity-aware
+ * visibility.
+ * jt_intersect_multi: ray i, its bound B (tmax[i]; +inf for tmax NULL) and instance[i] are exactly
+ * jt_intersect_bounded's: the scene query, or intersect_instance_bvh of one instance, of
+ * Ray3f(o, d, ray_eps, B) in the context's traversal. A *candidate* is a primitive the traversal
+ * tests whose test (intersect_triangle / intersect_quad, the closest-hit query's own) accepts it at
+ * the query's current tmax: ray_eps <= t <= tmax. Candidates are ordered by the key
+ * (t, instance, element): t compared as float32, the instance in the caller's numbering, all three
+ * ascending. The result is the k smallest keys, ascending, in hits[i k + 0 .. counts[i]); records
+ * counts[i] .. k - 1 are the miss record (-1, -1, 0, 0, +inf, 0); counts[i] <= k; u, v and t are
+ * the bits the primitive test produced. The current tmax is B while the list holds fewer than k
+ * entries and the k-th entry's t afterwards; every box test and primitive test reads it, as in
+ * the closest-hit query. A candidate that arrives at a full list is inserted iff its key is smaller
+ * than the last entry's, which is then dropped.
+ * There is no tie re-run: among the primitives a traversal tests the result does not depend on the
+ * order in which they are tested (a primitive among the k smallest has t <= every tmax the query
+ * ever holds, and the ids decide an equal t). The order can matter only where the reference's slab
+ * test culls a box that holds a hit (0 * inf for an axis-parallel ray from a box plane, rounding at
+ * a box edge): which boxes are asked, and at which tmax, depends on the child order and, in the
+ * wide order, on the quantised planes — the caveat of jt_traversal. k = 1 shrinks tmax exactly as
+ * the closest-hit query does, so its flag and t are jt_intersect_bounded's; the ids differ only at
+ * an exact-t tie: the smallest id here, the last one tested there.
+ * jt_count_hits: counts[i] is the number of candidates with tmax held at B throughout: no list,
+ * nothing shrinks, so every test reads the same tmax whatever the child order and the reference
+ * and near orders return the same count. An odd count from a point outside a closed mesh means
+ * the origin is inside it.
+ * The *_device variants take device pointers on the context's device (d_tmax and d_instance may be
+ * NULL; d_hits aligned to 8 bytes, d_counts to 4), run on the context's stream and return when it
+ * is idle; an instance id out of range gives count 0. The host variant of jt_intersect_multi runs
+ * the array in chunks of at most 2^22 / k rays through a buffer the context owns; a ray's result
+ * does not depend on the call's other rays, so the chunks give the bits of one call.
+ * The context is read only, as for every query.
+ * Errors: jt_intersect_bounded's, in its order and with its messages (outputs: hits, then counts);
+ * after the NULL and n checks, k < 1, k > JT_MULTI_MAX_HITS or n * k > 2^30 is JT_ERR_INVALID
+ * naming k; then the device variants' alignment; all before the context is looked at and before
+ * anything is written. n == 0 returns JT_OK with no device work. A NaN bound and non-finite rays
+ * are the caller's responsibility: every lane still ends in a bounded number of steps. */
+#define JT_MULTI_MAX_HITS 16
+int jt_intersect_multi(jt_ctx* ctx, int64_t n, const float* rays /* n x 6 */, const float* tmax /* n, or NULL */,
+                       const int32_t* instance /* or NULL */, int32_t k, jt_hit* hits /* n x k */, int32_t* counts /* n */);
+int jt_count_hits(jt_ctx* ctx, int64_t n, const float* rays, const float* tmax /* or NULL */,
+                  const int32_t* instance /* or NULL */, int32_t* counts /* n */);
+int jt_intersect_multi_device(jt_ctx* ctx, int64_t n, const void* d_rays, const void* d_tmax, const void* d_instance,
+                              int32_t k, void* d_hits, void* d_counts);
+int jt_count_hits_device(jt_ctx* ctx, int64_t n, const void* d_rays, const void* d_tmax, const void* d_instance, void* d_counts);
 
 /* ---- the surface at a hit ---------------------------------------------------------------- */
 /* What the integrator evaluates at a hit (src/scene.jl eval_shading_position, eval_shading_normal,

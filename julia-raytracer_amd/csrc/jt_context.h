@@ -109,18 +109,23 @@ struct jt_ctx {
     // Q_RAYS and its means in Q_OUT; the bounded queries (jt_intersect_bounded, jt_occluded_bounded)
     // stage their per-ray bounds in Q_TMAX, grown with the rays; jt_probe_sh's host variant stages a
     // chunk's 144-byte records in Q_SH (q_stage_sh records; at most probe_chunk points a chunk,
-    // jtr::PROBE_MAX_CHUNK unless the option test_probe_chunk lowers it)
+    // jtr::PROBE_MAX_CHUNK unless the option test_probe_chunk lowers it); jt_intersect_multi's host
+    // variant (jt_multihit.hip) stages a chunk's n x k jt_hit records in Q_MULTI (q_stage_multi
+    // records; the rays of a chunk: jtm::multi_chunk of k and the option test_multi_chunk) and,
+    // like jt_count_hits, its counts in Q_OUT
     std::vector<int> inst_new;
     int* q_to_dev = nullptr;
     int* q_to_ref = nullptr;
     unsigned* q_counter = nullptr;
-    enum { Q_OVF = 0, Q_RAYS, Q_INST, Q_OUT, Q_SURF, Q_TMAX, Q_SH, Q_NGROW };
-    void* q_grow[Q_NGROW] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    enum { Q_OVF = 0, Q_RAYS, Q_INST, Q_OUT, Q_SURF, Q_TMAX, Q_SH, Q_MULTI, Q_NGROW };
+    void* q_grow[Q_NGROW] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     size_t q_ovf_entries = 0;
     long long q_stage_rays = 0;
     long long q_stage_surf = 0;
     long long q_stage_sh = 0;
+    long long q_stage_multi = 0;
     long long probe_chunk = (long long)1 << 22;
+    long long multi_chunk = 0;  // option test_multi_chunk (tests only; 0: unset)
     // inst_nelem: the elements of each instance's shape, in the caller's numbering (jt_create);
     // uploaded by the first surface call (s_nelem, in `allocations`): surface_kernel's range check
     std::vector<int> inst_nelem;

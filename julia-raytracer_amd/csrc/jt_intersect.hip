@@ -472,6 +472,7 @@ void jtc::query_free(jt_ctx* c) {
     c->q_stage_rays = 0;
     c->q_stage_surf = 0;
     c->q_stage_sh = 0;
+    c->q_stage_multi = 0;
 }
 
 static_assert(sizeof(jt_hit) == 24, "the query kernel writes a jt_hit as six 32-bit words");

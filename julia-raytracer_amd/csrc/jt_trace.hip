@@ -324,6 +324,8 @@ int jt_create(const jt_scene* scene, const jt_scene_bvh* bvh, const jt_lights* l
     }
     // option test_probe_chunk (tests only): the points of a chunk of jt_probe_sh's host variant
     if (const char* pc = jt::opt(opts, "test_probe_chunk")) c->probe_chunk = jtr::probe_chunk(std::atoll(pc));
+    // option test_multi_chunk (tests only): the rays of a chunk of jt_intersect_multi's host variant
+    if (const char* mc = jt::opt(opts, "test_multi_chunk")) c->multi_chunk = std::atoll(mc);
     auto bail = [&](int status) {
         jt_destroy(c);
         return status;

@@ -355,6 +355,11 @@ def _declare(lib):
     lib.jt_probe_sh_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]
     lib.jt_sphere_rays.argtypes = [C.c_void_p, C.c_int64, f32p, C.c_int64, C.c_int32, f32p]
     lib.jt_sphere_rays_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
+    lib.jt_intersect_multi.argtypes = [C.c_void_p, C.c_int64, f32p, f32p, i32p, C.c_int32, C.POINTER(jt_hit), i32p]
+    lib.jt_count_hits.argtypes = [C.c_void_p, C.c_int64, f32p, f32p, i32p, i32p]
+    lib.jt_intersect_multi_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                              C.c_void_p]
+    lib.jt_count_hits_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.jt_reset.argtypes = [C.c_void_p]
     lib.jt_get_device_buffers.argtypes = [C.c_void_p, C.POINTER(jt_device_buffers)]
     lib.jt_set_counters.argtypes = [C.c_void_p, C.c_int32]
@@ -381,7 +386,10 @@ EXPORTED_SYMBOLS = [
     "jt_intersect_bounded_device", "jt_occluded_bounded_device", "jt_visible_device",
     "jt_ambient_occlusion", "jt_ambient_occlusion_device",
     "jt_probe_sh", "jt_probe_sh_device", "jt_sphere_rays", "jt_sphere_rays_device",
+    "jt_intersect_multi", "jt_count_hits", "jt_intersect_multi_device", "jt_count_hits_device",
 ]
+
+MULTI_MAX_HITS = 16  # JT_MULTI_MAX_HITS
 
 
 def load_library(path: str | os.PathLike | None = None):

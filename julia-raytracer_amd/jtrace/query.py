@@ -13,6 +13,13 @@ a bool array: whether nothing lies between the ends (jt_visible).
 
     python -m jtrace.query --scene scene.json --rays rays.npy --tmax 2.5 --any true --output shadowed.npy
     python -m jtrace.query --scene scene.json --segments links.npy --output visible.npy
+All hits along a ray (jt_intersect_multi, jt_count_hits): --hits K writes an .npz file with `hits`, (n, K)
+records of jt_hit's fields, the K nearest hits of every ray ordered by (t, instance, element), and
+`counts`, (n,) int32; --count true writes an (n,) int32 .npy, the primitives each ray crosses. Both
+honour --tmax and an (n, 7) file; neither goes with --any or --segments, nor with the other.
+
+    python -m jtrace.query --scene scene.json --rays rays.npy --hits 4 --output layers.npz
+    python -m jtrace.query --scene scene.json --rays rays.npy --count true --output crossings.npy
 The scene, camera, BVH and traversal flags are those of `python -m jtrace` (cli.py); nothing is
 traced. One line is printed: rays, hits, milliseconds of the query call.
 """
@@ -40,6 +47,8 @@ def _parser() -> argparse.ArgumentParser:
     p.add_argument("--tmax", type=float, default=None, help="one bound for all rays: hits up to t = tmax count")
     p.add_argument("--output", type=str, required=True, help=".npy file of the results")
     p.add_argument("--any", type=_bool, default=False, help="any-hit flags (jt_occluded) instead of closest hits")
+    p.add_argument("--hits", type=int, default=None, help="the K nearest hits of every ray (jt_intersect_multi), K = 1 .. 16: an .npz")
+    p.add_argument("--count", type=_bool, default=False, help="the number of hits of every ray (jt_count_hits): (n,) int32")
     p.add_argument("--camera", type=str, default="", help="camera name")
     p.add_argument("--highqualitybvh", type=_bool, default=False, help="enable high quality bvh")
     p.add_argument("--noparallel", type=_bool, default=False, help="disable threading")
@@ -53,6 +62,15 @@ def _parser() -> argparse.ArgumentParser:
 
 def run(ns, out=print) -> dict:
     segments = ns.rays is None
+    if ns.hits is not None or ns.count:
+        if segments:
+            raise SystemExit("--segments takes neither --hits nor --count: it writes visible flags")
+        if ns.any:
+            raise SystemExit("--any goes with neither --hits nor --count: give one")
+        if ns.hits is not None and ns.count:
+            raise SystemExit("--hits and --count: give one")
+        if ns.hits is not None and not 1 <= ns.hits <= abi.MULTI_MAX_HITS:
+            raise SystemExit(f"--hits {ns.hits}: expected 1 .. {abi.MULTI_MAX_HITS}")
     rays = np.load(ns.segments if segments else ns.rays)
     tmax = ns.tmax
     if segments:
@@ -78,8 +96,13 @@ def run(ns, out=print) -> dict:
                     traversal=ns.traversal)
     state = make_trace_state(scene_abi, bvh, lights, abi.make_params(params, camera), lib)
     t0 = time.perf_counter()
+    counts = None
     if segments:
         result = state.visible(rays)
+    elif ns.hits is not None:
+        result, counts = state.intersect_multi(rays, ns.hits, tmax=tmax)
+    elif ns.count:
+        result = state.count_hits(rays, tmax=tmax)
     else:
         result = state.occluded(rays, tmax=tmax) if ns.any else state.intersect(rays, tmax=tmax)
     ms = (time.perf_counter() - t0) * 1e3
@@ -87,7 +110,15 @@ def run(ns, out=print) -> dict:
     state.close()
     # through a file object: np.save then keeps the name as given (no ".npy" appended)
     with open(ns.output, "wb") as f:
-        np.save(f, result)
+        if counts is not None:
+            np.savez(f, hits=result, counts=counts)
+        else:
+            np.save(f, result)
+    if counts is not None or ns.count:
+        total = int((result if counts is None else counts).sum())
+        what = f"the {ns.hits} nearest hits" if counts is not None else "hit counts"
+        out(f"{len(rays)} rays, {total} hits, {ms:.3f} ms ({what}{'' if tmax is None else ', bounded'}, traversal {traversal})")
+        return {"rays": len(rays), "hits": total, "ms": ms}
     if segments:
         visible = int(result.sum())
         out(f"{len(rays)} segments, {visible} visible, {ms:.3f} ms (traversal {traversal})")

@@ -350,6 +350,88 @@ class TraceState:
                                                 out.ctypes.data_as(abi.u8p)))
         return out != 0
 
+    # --- all hits along a ray (jt_intersect_multi, jt_count_hits: include/jtrace.h)
+    def _host_instance(self, instance, n):
+        if instance is None:
+            return None, None
+        instance = np.ascontiguousarray(instance, np.int32)
+        if instance.shape != (n,):
+            raise ValueError(f"instance: expected shape ({n},), got {instance.shape}")
+        return instance, instance.ctypes.data_as(abi.i32p)
+
+    def intersect_multi(self, rays, k, instance=None, tmax=None):
+        """jt_intersect_multi: the k nearest hits of every ray (n, 6), ordered by (t, instance,
+        element), in one traversal: (records, counts). numpy rays give records (n, k) of abi.HIT_DTYPE
+        (slots counts[i] .. k - 1 hold the miss record) and counts (n,) int32; a torch tensor on the
+        context's device goes zero-copy through jt_intersect_multi_device and gives an int32
+        (n, k, 6) tensor and an int32 (n,) tensor. instance and tmax as intersect's."""
+        k = int(k)
+        if tmax is not None:
+            tmax = self._bounds(rays, tmax)
+        if hasattr(rays, "data_ptr"):
+            torch, n = self._device_rays(rays, instance)
+            if not 1 <= k <= abi.MULTI_MAX_HITS:
+                raise ValueError(f"k: expected 1 .. {abi.MULTI_MAX_HITS}, got {k}")
+            out = torch.empty((n, k, 6), dtype=torch.int32, device=rays.device)
+            counts = torch.empty(n, dtype=torch.int32, device=rays.device)
+            abi.check(self.lib, self.lib.jt_intersect_multi_device(self.handle, n, rays.data_ptr(),
+                                                                   None if tmax is None else tmax.data_ptr(),
+                                                                   None if instance is None else instance.data_ptr(), k,
+                                                                   out.data_ptr(), counts.data_ptr()))
+            return out, counts
+        rays = _host_rays(rays)
+        n = len(rays)
+        instance, ip = self._host_instance(instance, n)
+        out = np.empty((n, max(k, 0)), abi.HIT_DTYPE)
+        counts = np.empty(n, np.int32)
+        abi.check(self.lib, self.lib.jt_intersect_multi(self.handle, n, rays.ctypes.data_as(abi.f32p),
+                                                        None if tmax is None else tmax.ctypes.data_as(abi.f32p), ip, k,
+                                                        out.ctypes.data_as(C.POINTER(abi.jt_hit)), counts.ctypes.data_as(abi.i32p)))
+        return out, counts
+
+    def count_hits(self, rays, tmax=None, instance=None):
+        """jt_count_hits: int32 (n,), the primitives every ray crosses within ray_eps <= t <= tmax
+        (None: unbounded), tmax held throughout; an odd count from outside a closed mesh means the
+        origin is inside it. numpy gives numpy, a torch tensor on the context's device a tensor there."""
+        if tmax is not None:
+            tmax = self._bounds(rays, tmax)
+        if hasattr(rays, "data_ptr"):
+            torch, n = self._device_rays(rays, instance)
+            counts = torch.empty(n, dtype=torch.int32, device=rays.device)
+            abi.check(self.lib, self.lib.jt_count_hits_device(self.handle, n, rays.data_ptr(),
+                                                              None if tmax is None else tmax.data_ptr(),
+                                                              None if instance is None else instance.data_ptr(), counts.data_ptr()))
+            return counts
+        rays = _host_rays(rays)
+        n = len(rays)
+        instance, ip = self._host_instance(instance, n)
+        counts = np.empty(n, np.int32)
+        abi.check(self.lib, self.lib.jt_count_hits(self.handle, n, rays.ctypes.data_as(abi.f32p),
+                                                   None if tmax is None else tmax.ctypes.data_as(abi.f32p), ip,
+                                                   counts.ctypes.data_as(abi.i32p)))
+        return counts
+
+    def transmittance(self, rays, tmax=None, k: int = 8):
+        """(T, complete): T = the product of (1 - opacity) over a ray's first k hits, nearest first,
+        in float32, from surfaces() of intersect_multi's records; complete = counts < k, the list
+        holds every hit of the ray. The opacity-aware visibility that the first-hit queries
+        (occluded, visible, gbuffer) do not give. Python only: two library calls."""
+        recs, counts = self.intersect_multi(rays, k, tmax=tmax)
+        if hasattr(rays, "data_ptr"):
+            n = len(rays)
+            surf = split_surfaces(self.surfaces(rays.repeat_interleave(k, dim=0).contiguous(), recs.reshape(n * k, 6)))
+            through = 1 - surf["opacity"].reshape(n, k)
+            through[recs[:, :, 5] == 0] = 1
+            T = through[:, 0].clone()
+        else:
+            rays = _host_rays(rays)
+            surf = self.surfaces(np.repeat(rays, k, axis=0), recs.reshape(-1))
+            through = np.where(recs["hit"] != 0, np.float32(1) - surf["opacity"].reshape(len(rays), k), np.float32(1)).astype(np.float32)
+            T = through[:, 0].copy()
+        for j in range(1, k):
+            T = T * through[:, j]
+        return T, counts < k
+
     # --- the surface at a hit (jt_eval_hits, jt_camera_rays, jt_gbuffer: include/jtrace.h)
     def _torch_device(self):
         """torch and the context's device, for the calls that return device tensors."""
