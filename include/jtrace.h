@@ -335,7 +335,12 @@ int jt_device_count(int32_t* out);
  *   "test_probe_chunk" "<n>"  (tests only) jt_probe_sh's host variant stages at most n points per
  *                            chunk instead of 2^22: a chunk boundary on a small array
  *   "test_multi_chunk" "<n>"  (tests only) jt_intersect_multi's host variant stages at most n rays
- *                            per chunk instead of 2^22 / k */
+ *                            per chunk instead of 2^22 / k
+ *   "test_trace_chunk" "<n>"  (tests only) a one-stream context (batch <= 1) traces a range of more
+ *                            than one sample in chunks of at most n samples instead of up to 64:
+ *                            n a power of two in [1, 64] (jt_create fails with JT_ERR_INVALID
+ *                            otherwise); 1: no chunks, one launch of the whole range. It only ever
+ *                            lowers the chunk */
 int jt_set_option(const char* name, const char* value);
 
 /* ---- host helpers (CPU only) ------------------------------------------------------- */

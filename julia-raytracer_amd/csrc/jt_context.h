@@ -61,6 +61,7 @@ struct jt_ctx {
     // `chunk` samples, each traced as one-sample streams into the stream-mean buffers (allocated at
     // the first such flush) and folded into the running mean by chain_kernel in sample order
     int chunk = 0;
+    int trace_chunk = 0;  // option test_trace_chunk (tests only; 0: unset): a cap on `chunk`
     // two sets of chunk buffers: chunk i traces into set i & 1 on `stream` while chain_kernel folds
     // chunk i - 1 on `stream2` (the chains stay in sample order on stream2; a trace reuses a set
     // only after the chain that read it, chain_done)

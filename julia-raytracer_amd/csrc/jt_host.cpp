@@ -30,7 +30,7 @@ static std::map<std::string, std::string> g_opts;
 static const char* const kOptionNames[] = {
     "env_alias",  "features",    "lds_scene",   "lds_stack",  "light_inline", "streams",
     "wait_lanes", "light_lanes", "multi_split", "tile_share",  "test_lds_ring",
-    "test_probe_chunk", "test_multi_chunk",
+    "test_probe_chunk", "test_multi_chunk", "test_trace_chunk",
 };
 std::map<std::string, std::string> options_snapshot() {
     std::lock_guard<std::mutex> g(g_opt_mu);

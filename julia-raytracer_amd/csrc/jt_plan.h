@@ -1,6 +1,6 @@
 // jt_plan.h — the launch plan of a context as integer functions: which 8x8 tiles a launch covers,
 // which pixel a launch slot is, how many sample streams a context keeps, the stream weights of a
-// combine, the chunk size of a one-stream context and a device's share of a batch. Plain C++ (no
+// combine, the chunk size and chunk schedule of a one-stream context and a device's share of a batch. Plain C++ (no
 // HIP runtime), shared by the kernels, the device context and the host check (tests/plan_check.cpp).
 #pragma once
 
@@ -124,6 +124,38 @@ JT_PLAN_HD int chunk_samples(long long nslot) {
     int m = JT_MAX_STREAMS;
     while (m > 1 && 2 * nslot * m > JT_STREAM_ITEMS_MAX) m >>= 1;
     return m;
+}
+
+// the option test_trace_chunk (tests only) as a cap on that chunk size: n itself when it is a power
+// of two in [1, 64], 0 (jt_create rejects the option) otherwise. The cap only ever lowers the chunk.
+JT_PLAN_HD int chunk_cap(long long n) { return n >= 1 && n <= JT_MAX_STREAMS && (n & (n - 1)) == 0 ? (int)n : 0; }
+
+// The chunk schedule of a one-stream range [s0, s1) at chunk size `chunk` > 1 (trace_launch,
+// jt_trace.hip): chunk i of chunk_count traces samples [x, y) as one-sample streams of a launch with
+// DParams::first = x and DParams::lk = lk into buffer set `set`, and chain_kernel folds its y - x
+// records into the running mean.
+// Every chunk goes through the chunk buffers, a one-sample tail included: lk >= 1 always, since a
+// launch with lk == 0 stores into the running mean itself, which the previous chunk's chain is
+// still writing on the second stream, and leaves the chunk's buffer set unwritten for its own chain.
+// So lk is the smallest value >= 1 with 2^lk >= y - x; a tail of one sample is stream 0 of a
+// two-stream launch (the launch's stream slots are min(y - x, 2^lk) = 1), folded with m = 1 like any
+// other chunk: one code path and one launch shape, where a plain lk == 0 launch of the tail would
+// need a wait of its own on the last chain and no chain launch.
+struct ChunkPlan {
+    int x, y;  // the chunk's global samples [x, y)
+    int lk;    // log2 of its launch's streams
+    int set;   // its buffer set, i & 1
+};
+JT_PLAN_HD int chunk_lk(int len) {
+    int lk = 1;
+    while ((1 << lk) < len) lk++;
+    return lk;
+}
+JT_PLAN_HD int chunk_count(int s0, int s1, int chunk) { return (int)(((long long)s1 - s0 + chunk - 1) / chunk); }
+JT_PLAN_HD ChunkPlan chunk_plan(int s0, int s1, int chunk, int i) {
+    const long long x = (long long)s0 + (long long)i * chunk;
+    const long long y = x + chunk < s1 ? x + chunk : s1;
+    return ChunkPlan{(int)x, (int)y, chunk_lk((int)(y - x)), i & 1};
 }
 
 // the contiguous share [*a, *b) of device d of D of the batch [s0, s1) under the sample split

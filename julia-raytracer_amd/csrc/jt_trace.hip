@@ -304,6 +304,12 @@ int jt_create(const jt_scene* scene, const jt_scene_bvh* bvh, const jt_lights* l
     PreparedScene ps;
     int st = prepare_scene(scene, bvh, lights, params, opts, ps);
     if (st != JT_OK) return st;
+    // option test_trace_chunk (tests only): a cap on a one-stream context's chunk (ensure_chunk), a
+    // power of two in [1, 64] (chunk_cap, jt_plan.h); 1: no chunks, as when their buffers fail
+    int trace_chunk = 0;
+    if (const char* tc = jt::opt(opts, "test_trace_chunk"))
+        if (!(trace_chunk = chunk_cap(std::atoll(tc))))
+            return jt::fail(JT_ERR_INVALID, "option test_trace_chunk: not a power of two in [1, 64]");
 
     hipError_t e = hipSetDevice(params->device);
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
@@ -326,6 +332,7 @@ int jt_create(const jt_scene* scene, const jt_scene_bvh* bvh, const jt_lights* l
     if (const char* pc = jt::opt(opts, "test_probe_chunk")) c->probe_chunk = jtr::probe_chunk(std::atoll(pc));
     // option test_multi_chunk (tests only): the rays of a chunk of jt_intersect_multi's host variant
     if (const char* mc = jt::opt(opts, "test_multi_chunk")) c->multi_chunk = std::atoll(mc);
+    c->trace_chunk = trace_chunk;
     auto bail = [&](int status) {
         jt_destroy(c);
         return status;
@@ -473,11 +480,14 @@ extern "C" int jt_reset(jt_ctx* c) {
 namespace {
 // the chunk buffers of a one-stream context (chunk_samples, jt_plan.h), allocated at the first
 // multi-sample range, the chunk halved on NOMEM. jt_ctx::chunk: 0 after jt_create (none yet), 1:
-// none possible (the range then runs as one launch of long items).
+// none possible (the range then runs as one launch of long items). The option test_trace_chunk
+// (tests only, jt_ctx::trace_chunk) lowers the size chunk_samples gives; at 1 it takes the path of
+// a second stream, an event or an allocation that failed.
 int ensure_chunk(jt_ctx* c) {
     if (c->chunk) return JT_OK;
     const long long nslot = (long long)launch_tiles(c->P) * 64;
     int m = chunk_samples(nslot);
+    if (c->trace_chunk && c->trace_chunk < m) m = c->trace_chunk;  // option test_trace_chunk: lowers it only
     (void)hipSetDevice(c->device);
     if (hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking) != hipSuccess) {
         c->stream2 = nullptr;
@@ -535,14 +545,18 @@ int trace_launch(jt_ctx* c, int32_t s0, int32_t s1, int32_t first) {
         // chunk i traces into buffer set i & 1 on `stream`; its chain runs on `stream2` after that
         // trace and after chain i - 1 (stream order), overlapping trace i + 1; trace i + 2 reuses
         // the set once chain i has read it. `stream` then waits for the last chain (ev1 covers it).
-        int i = 0;
-        for (int32_t x = s0; x < s1; x += c->chunk, i++) {
-            const int32_t y = std::min(s1, x + c->chunk);
-            const int set = i & 1;
+        // Which samples, which stream count and which set: chunk_plan (jt_plan.h). A one-sample
+        // tail goes through the chunk buffers like every other chunk (lk >= 1) rather than as a plain
+        // lk == 0 launch behind a wait for the last chain: one code path and one launch shape, and
+        // no launch that stores into the running mean while a chain is writing it.
+        const int nchunk = chunk_count(s0, s1, c->chunk);
+        for (int i = 0; i < nchunk; i++) {
+            const ChunkPlan cp = chunk_plan(s0, s1, c->chunk, i);
+            const int32_t x = cp.x, y = cp.y;
+            const int set = cp.set;
             DParams P = c->P;  // the chunk's samples as one-sample streams x .. y-1
             P.first = x;
-            P.lk = 0;
-            while ((1 << P.lk) < y - x) P.lk++;
+            P.lk = cp.lk;
             DAccum A = c->A;
             A.part_img = c->cpart[set][0];
             A.part_alb = c->cpart[set][1];
@@ -559,7 +573,7 @@ int trace_launch(jt_ctx* c, int32_t s0, int32_t s1, int32_t first) {
             if ((e = hipEventRecord(c->chain_done[set], c->stream2)) != hipSuccess) return hip_fail(e, "hipEventRecord");
             launches++;
         }
-        if ((e = hipStreamWaitEvent(c->stream, c->chain_done[(i - 1) & 1], 0)) != hipSuccess)
+        if ((e = hipStreamWaitEvent(c->stream, c->chain_done[(nchunk - 1) & 1], 0)) != hipSuccess)
             return hip_fail(e, "hipStreamWaitEvent");
     } else {
         c->P.first = first;

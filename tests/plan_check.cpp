@@ -10,7 +10,22 @@
 //     (float)((double)n_j / n), and two rows pinned from tests/error_ref.py stream_weights;
 //   - sample_share: contiguous, disjoint shares that cover the batch;
 //   - chunk_samples: a power of two in [1, 64], the largest whose two buffer sets stay within
-//     2^27 records.
+//     2^27 records; chunk_cap (option test_trace_chunk): a power of two in [1, 64] or rejected;
+//   - the chunk schedule of a one-stream range (chunk_count, chunk_plan, chunk_lk), for every chunk
+//     size 2 .. 64 and every range of 2 .. 200 samples from the starts 0, 1 and 7:
+//       (a) the chunks tile [s0, s1) once and in order, ceil(n / chunk) of them, none empty and
+//           only the last shorter than the chunk size;
+//       (b) every chunk has lk >= 1 and 2^lk >= y - x;
+//       (c) lk is the smallest such value >= 1 (a tail of one sample has lk = 1, not the 0 that
+//           2^lk >= 1 alone would give);
+//       (d) set == i & 1.
+//     trace_launch (csrc/jt_trace.hip) relies on (a) for which samples are traced, and on (b) for
+//     the fix of the one-sample tail: a launch with lk == 0 stores into the running mean, not into
+//     its buffer set, while the previous chunk's chain_kernel writes that mean on the second
+//     stream, and the chunk's own chain then folds a set this launch never wrote. With lk >= 1
+//     every chunk's records land in its set (2^lk >= y - x: no two samples share a stream, so each
+//     record is one sample's value) and chain_kernel folds y - x of them. (d) is what the
+//     chain_done wait of chunk i >= 2 assumes: the set was last read by chain i - 2.
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -93,6 +108,47 @@ void check_weights() {
     check(ok, "combine_weights(32, k = 16) against the pinned row");
 }
 
+void check_chunks() {
+    for (long long n = -2; n <= 130; n++) {
+        const bool pow2 = n >= 1 && n <= 64 && (n & (n - 1)) == 0;
+        check(jtk::chunk_cap(n) == (pow2 ? n : 0), "chunk_cap", n);
+    }
+    check(jtk::chunk_cap(1LL << 40) == 0 && jtk::chunk_cap(-64) == 0, "chunk_cap: far values");
+    for (int chunk = 2; chunk <= 64; chunk *= 2)
+        for (int s0 : {0, 1, 7})
+            for (int n = 2; n <= 200; n++) {
+                const int s1 = s0 + n, count = jtk::chunk_count(s0, s1, chunk);
+                check(count == (n + chunk - 1) / chunk, "chunk_count", chunk, s0, n, count);
+                int end = s0;  // (a): the chunks follow each other from s0 to s1
+                bool tiled = true, through = true, smallest = true, sets = true;
+                for (int i = 0; i < count; i++) {
+                    const jtk::ChunkPlan p = jtk::chunk_plan(s0, s1, chunk, i);
+                    const int len = p.y - p.x;
+                    tiled = tiled && p.x == end && len >= 1 && len <= chunk && (len == chunk || i == count - 1);
+                    end = p.y;
+                    through = through && p.lk >= 1 && (1 << p.lk) >= len;                   // (b)
+                    smallest = smallest && (p.lk == 1 || (1 << (p.lk - 1)) < len);          // (c)
+                    sets = sets && p.set == (i & 1);                                        // (d)
+                    check(p.lk == jtk::chunk_lk(len), "chunk_plan: lk is not chunk_lk of its length", chunk, s0, n, i);
+                }
+                check(tiled && end == s1, "chunk_plan: the chunks do not tile the range in order", chunk, s0, n);
+                check(through, "chunk_plan: a chunk misses the chunk buffers (lk < 1 or 2^lk < y - x)", chunk, s0, n);
+                check(smallest, "chunk_plan: lk is not the smallest", chunk, s0, n);
+                check(sets, "chunk_plan: set != i & 1", chunk, s0, n);
+            }
+    // the tails the schedule used to get wrong, and the natural chunk's: 64 + 1, 32 + 1, 8 + 1
+    const int tails[][2] = {{64, 65}, {32, 33}, {8, 9}, {4, 9}, {2, 3}};  // chunk size, samples
+    for (const auto& r : tails) {
+        const jtk::ChunkPlan p = jtk::chunk_plan(0, r[1], r[0], jtk::chunk_count(0, r[1], r[0]) - 1);
+        check(p.x == r[1] - 1 && p.y == r[1] && p.lk == 1, "a tail of one sample", r[0], r[1], p.lk);
+    }
+    check(jtk::chunk_lk(1) == 1 && jtk::chunk_lk(2) == 1 && jtk::chunk_lk(3) == 2 && jtk::chunk_lk(64) == 6, "chunk_lk pins");
+    // a range that ends at the last sample index: no overflow past s1
+    const int top = 0x7fffffff;
+    const jtk::ChunkPlan last = jtk::chunk_plan(top - 65, top, 64, 1);
+    check(jtk::chunk_count(top - 65, top, 64) == 2 && last.x == top - 1 && last.y == top && last.lk == 1, "the last sample index");
+}
+
 }  // namespace
 
 int main() {
@@ -134,6 +190,8 @@ int main() {
         check(m == 1 || 2 * nslot * m <= (1LL << 27), "chunk_samples: above 2^27 records", tiles, m);
         check(m == 64 || 2 * nslot * (2 * m) > (1LL << 27), "chunk_samples: not the largest", tiles, m);
     }
+
+    check_chunks();
 
     std::printf("plan_check: %ld cases, %ld bad\n", cases, bad);
     return bad ? 1 : 0;
