@@ -92,6 +92,63 @@ __device__ __forceinline__ v3 sample_sphere(v2 ruv) {
     jl_sincos(phi, &s, &c);
     return normalize(V3(r * c, r * s, z));
 }
+
+// ---------------------------------------------------------------- baked shading (JT_SHADE_BAKE)
+// What a matte bounce of an FT_NONE kernel recomputes from constants of the scene, computed once
+// per workgroup instead (bake_shading, jt_kernels.h; shade_baked, jt_traverse.h):
+//   * basis_fromz(n) of the element normal n: in these kernels the normal that sample_bsdfcos hands
+//     to sample_hemisphere_cos is n or -n (no vertex normals, no normal map, no instance rotation);
+//   * color / pi of eval_matte: the material's colour times no texture and no vertex colour.
+// Six of the basis's nine entries are stored, (X.x, Y.x, Y.y, Z); X.y = sign * Y.x, X.z = -sign * Z.x
+// and Y.z = -Z.y with sign = copysign(1, Z.z) are one multiplication or one sign change of stored
+// values, the same operations basis_fromz itself applies to them.
+//
+// Orientation. With z = normalize(n), s = copysign(1, z.z), a = -1 / (s + z.z), b = z.x * z.y * a,
+// basis_fromz(n) is X = (1 + s z.x z.x a, s b, -s z.x), Y = (b, s + z.y z.y a, -z.y), Z = z. For -n
+// every input changes sign and nothing else: normalize is odd (dot(n, n) is even, a division by the
+// same length is odd, the zero vector comes back as it is), copysign(1, -z.z) = -s also at z.z = +-0,
+// s + z.z is never 0 (|s + z.z| >= 1), so its negation is exact and a becomes -a, b = (z.x z.y) a
+// becomes -b. A product of correctly rounded factors changes sign exactly with an odd number of
+// them, so X.x, X.y and X.z keep their bits and Y.x, Y.z and Z change sign. The one entry that is a
+// sum which can cancel is Y.y = s + z.y z.y a: at n = (+-0, +-1, +-0) it is 1 + -1 or -1 + 1, +0 in both
+// orientations (round to nearest), not -0 in one. So basis_fromz(-n) = (X, -Y, -Z) of basis_fromz(n)
+// with Y.y' = 0 - Y.y, a subtraction: -Y.y where Y.y != 0, +0 where it is 0 (Y.y is never -0). The
+// difference shows: with ruv.y = 0 the sample's y component is a sum of zeros that takes Y.y's sign,
+// and 1 / d of the next ray its infinity's. tests/shade_bake_check.cpp enumerates all of this on the
+// host, bit for bit.
+struct BakedBasis {
+    v3 n;              // the element normal as stored
+    float xx, yx, yy;  // X.x, Y.x, Y.y of basis_fromz(n)
+    v3 z;              // Z = normalize(n)
+};
+__device__ __forceinline__ m3 basis_baked(const BakedBasis& k, bool flip) {  // basis_fromz(flip ? -n : n)
+    const v3 z = flip ? -k.z : k.z;
+    const float b = flip ? -k.yx : k.yx;
+    const float sign = __builtin_copysignf(1.0f, z.z);
+    return m3{V3(k.xx, sign * b, -sign * z.x), V3(b, flip ? 0.0f - k.yy : k.yy, -z.y), z};
+}
+// sample_bsdfcos of a matte point whose shading normal is eval_shading's orientation of k.n: that
+// predicate and up_normal's on the oriented normal, each as the reference evaluates it (they differ
+// at dot == +-0), XORed, say whether `up` is -k.n. load() reads the element's BakedBasis: after the
+// local sample, behind a compiler barrier — hoisted above the sine and cosine, its nine values cost
+// the headline kernel two spilled VGPRs and four more spilled SGPRs.
+// (sample_hemisphere_cos's lines are restated, not shared: routed through a common function, every
+// other kernel's register allocation changed)
+template <class Load>
+__device__ __forceinline__ v3 sample_matte_baked(Load load, float roughness, v3 outgoing, v2 rn) {
+    if (roughness == 0) return V3(0, 0, 0);
+    float z = __builtin_sqrtf(rn.y);
+    float r = __builtin_sqrtf(1 - z * z);
+    float phi = 2 * pif * rn.x;
+    float s, c;
+    jl_sincos(phi, &s, &c);
+    const v3 local = V3(r * c, r * s, z);
+    __asm__ volatile("" ::: "memory");
+    const BakedBasis k = load();
+    const bool flip = !(dot(k.n, outgoing) >= 0);  // eval_shading: normal = dot(n, o) >= 0 ? n : -n
+    const v3 normal = flip ? -k.n : k.n;
+    return normalize(mul(basis_baked(k, flip != (dot(normal, outgoing) <= 0)), local));  // up_normal
+}
 // GGX microfacet_distribution / shadowing / sampling (src/shading.jl:734-816)
 __device__ __forceinline__ float microfacet_distribution(float roughness, v3 normal, v3 halfway) {
     float cosine = dot(normal, halfway);
@@ -411,6 +468,14 @@ __device__ __forceinline__ void eval_bsdfcos_pdf(const MatPoint& m, v3 n, v3 o, 
             return;
         default: return;
     }
+}
+// the same of a matte point with baked shading: eval_matte on the baked color / pif
+__device__ __forceinline__ void eval_matte_pdf_baked(v3 color_pi, float roughness, v3 n, v3 o, v3 i, v3& f, float& pdf) {
+    f = V3(0, 0, 0);
+    pdf = 0;
+    if (roughness == 0) return;
+    if (!(dot(n, i) * dot(n, o) <= 0)) f = color_pi * __builtin_fabsf(dot(n, i));
+    pdf = sample_matte_pdf(n, o, i);
 }
 template <int F>
 __device__ __forceinline__ v3 eval_delta(const MatPoint& m, v3 n, v3 o, v3 i) {  // :757-778

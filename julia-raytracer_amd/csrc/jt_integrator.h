@@ -388,7 +388,8 @@ struct NoAov {};
 template <int F>
 __device__ __forceinline__ void aov_update(const NoAov&, v3, v3) {}
 
-template <int F, class AovT>
+// SB: the kernel shades from its baked copy (shade_baked, jt_traverse.h; BakedShade, jt_scene_eval.h)
+template <int F, bool SB = false, class AovT>
 __device__ __forceinline__ bool path_hit(const DScene& S, const DParams& P, Path& st, Hit isec, const AovT& aov,
                                          unsigned& shades) {
     if (!isec.hit) {
@@ -409,7 +410,8 @@ __device__ __forceinline__ bool path_hit(const DScene& S, const DParams& P, Path
     if (!in_volume) {  // surface (:328-423)
         v3 outgoing = -st.d;
         Shading sh;
-        eval_shading<F>(S, isec.inst, isec.elem, V2(isec.u, isec.v), outgoing, sh);
+        BakedShade bk;
+        eval_shading<F, SB>(S, isec.inst, isec.elem, V2(isec.u, isec.v), outgoing, sh, &bk);
         shades++;
         if (P.nocaustics) {
             st.set_max_roughness<F>(jl_max(sh.mat.roughness, st.max_roughness<F>()));
@@ -432,7 +434,8 @@ __device__ __forceinline__ bool path_hit(const DScene& S, const DParams& P, Path
             if (rand1f(st.rng) < 0.5f) {
                 float rnl = rand1f(st.rng);
                 v2 rn = rand2f(st.rng);
-                incoming = sample_bsdfcos<F>(sh.mat, sh.normal, outgoing, rnl, rn);
+                if constexpr (SB) incoming = sample_matte_baked([&] { return baked_basis(S, bk.elem); }, sh.mat.roughness, outgoing, rn);
+                else incoming = sample_bsdfcos<F>(sh.mat, sh.normal, outgoing, rnl, rn);
             } else {
                 float rl = rand1f(st.rng), rel = rand1f(st.rng);
                 v2 ruv = rand2f(st.rng);
@@ -442,7 +445,8 @@ __device__ __forceinline__ bool path_hit(const DScene& S, const DParams& P, Path
 #if JT_FUSED_BSDF
             v3 fb;
             float pbv;
-            eval_bsdfcos_pdf<F>(sh.mat, sh.normal, outgoing, incoming, fb, pbv);
+            if constexpr (SB) eval_matte_pdf_baked(baked_color_pi(S, bk.material), sh.mat.roughness, sh.normal, outgoing, incoming, fb, pbv);
+            else eval_bsdfcos_pdf<F>(sh.mat, sh.normal, outgoing, incoming, fb, pbv);
             st.set_weight<F>(st.weight<F>() * fb);
             st.set_pb<F>(pbv);
 #else
@@ -495,7 +499,7 @@ __device__ __forceinline__ bool path_hit(const DScene& S, const DParams& P, Path
 }
 
 // trace_naive's bounce body after the closest-hit query (src/trace.jl:490-569)
-template <int F, class AovT>
+template <int F, bool SB = false, class AovT>
 __device__ __forceinline__ bool naive_hit(const DScene& S, const DParams& P, Path& st, Hit isec, const AovT& aov,
                                           unsigned& shades) {
     if (!isec.hit) {
@@ -505,7 +509,8 @@ __device__ __forceinline__ bool naive_hit(const DScene& S, const DParams& P, Pat
     }
     v3 outgoing = -st.d;
     Shading sh;
-    eval_shading<F>(S, isec.inst, isec.elem, V2(isec.u, isec.v), outgoing, sh);
+    BakedShade bk;
+    eval_shading<F, SB>(S, isec.inst, isec.elem, V2(isec.u, isec.v), outgoing, sh, &bk);
     shades++;
     if ((F & FT_OPAC) && sh.mat.opacity < 1 && rand1f(st.rng) >= sh.mat.opacity) {
         if (st.opbounce() > 128) return true;
@@ -523,10 +528,12 @@ __device__ __forceinline__ bool naive_hit(const DScene& S, const DParams& P, Pat
     if (sh.mat.roughness != 0) {
         float rnl = rand1f(st.rng);
         v2 rn = rand2f(st.rng);
-        incoming = sample_bsdfcos<F>(sh.mat, sh.normal, outgoing, rnl, rn);
+        if constexpr (SB) incoming = sample_matte_baked([&] { return baked_basis(S, bk.elem); }, sh.mat.roughness, outgoing, rn);
+        else incoming = sample_bsdfcos<F>(sh.mat, sh.normal, outgoing, rnl, rn);
         if (is_zero(incoming)) return true;
 #if JT_FUSED_BSDF
-        eval_bsdfcos_pdf<F>(sh.mat, sh.normal, outgoing, incoming, f, p);
+        if constexpr (SB) eval_matte_pdf_baked(baked_color_pi(S, bk.material), sh.mat.roughness, sh.normal, outgoing, incoming, f, p);
+        else eval_bsdfcos_pdf<F>(sh.mat, sh.normal, outgoing, incoming, f, p);
 #else
         f = eval_bsdfcos<F>(sh.mat, sh.normal, outgoing, incoming);
         p = sample_bsdfcos_pdf<F>(sh.mat, sh.normal, outgoing, incoming);

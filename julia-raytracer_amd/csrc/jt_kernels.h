@@ -285,6 +285,7 @@ __device__ __forceinline__ void trace_body_items(const DScene& S0, const DParams
     const DParams& P = P0;
     static_assert(lane_lds(F), "the per-lane item body keeps the lane's sample index in LDS");
     constexpr int PB = push_bit(node_baked<OVF, NCACHE, WIDE, F>());  // the push mask's bit of a baking kernel
+    constexpr bool SB = shade_baked<OVF, NCACHE, WIDE, F>();          // its matte bounces read the baked shading
     const int lane = threadIdx.x & 63;
     const int oslot = (int)blockIdx.x * BLOCK + (int)threadIdx.x;  // the lane's HBM stack-overflow area
     if constexpr ((F & (FT_TEX | FT_ENV)) != 0) {  // the texel-decode LUTs into LDS (tex_lut)
@@ -567,8 +568,8 @@ __device__ __forceinline__ void trace_body_items(const DScene& S0, const DParams
             bool done;
             if (LSTEP && st.phase == PH_FINISH) done = true;
             else if (light) done = light_hit<F>(S, P, st, query_hit(T));
-            else if (SAMPLER == 2) done = naive_hit<F>(S, P, st, query_hit(T), aov, cnt.shades);
-            else done = path_hit<F>(S, P, st, query_hit(T), aov, cnt.shades);
+            else if (SAMPLER == 2) done = naive_hit<F, SB>(S, P, st, query_hit(T), aov, cnt.shades);
+            else done = path_hit<F, SB>(S, P, st, query_hit(T), aov, cnt.shades);
             bool chained = false;  // the lane ran its bounce's light chains here (query_restart below)
             if (SAMPLER == 1 && !done && st.phase == PH_LIGHT && chains_inline(F, S)) {
                 unsigned nlq = 0;
@@ -769,6 +770,40 @@ __device__ __forceinline__ void bake_nodes(const DScene& S, uint4* blob) {
     }
 }
 
+// Baked shading (shade_baked, jt_traverse.h; BakedBasis, jt_bsdf.h), in the same pass: per element g
+// of the LDS copy basis_fromz of its normal enrm_id[g], per material color / pif, written with the
+// device functions the matte bounce would call, into bytes of the copy that a kernel without scene
+// features never reads:
+//   enrm[g] (Z, X.x)       element_normal reads enrm only for an instance that is not rot_identity;
+//                          without FT_XFORM a scene has none (layout_scene), and eval_shading<F, true>
+//                          reads enrm_id without looking
+//   enrm_id[g].w (Y.x)     xyz() of the row is the normal; nothing reads w
+//   elems[g].w (Y.y)       the fourth vertex of a quad: read under FT_QUAD only
+//   DMaterial::scattering  MatPoint::scattering feeds the volume stack: FT_VOL only
+// The arrays lie in JT_SCENE_ARRAYS' order, one 16-B unit per element in elems, enrm and enrm_id
+// alike (an empty array keeps one unit in each: a harmless write), six units per material up to the
+// lights. A thread reads and writes rows of its own element or material only, and nothing reads
+// them before the barrier. The host's bytes (hs.*, the blob in HBM) are not touched.
+__device__ __forceinline__ void bake_shading(const DScene& S, uint4* blob) {
+    static_assert(sizeof(DMaterial) == 6 * 16, "six 16-B units per material");
+    const int nelem = S.o_enrm_id - S.o_enrm;
+    for (int g = threadIdx.x; g < nelem; g += BLOCK) {
+        float4& ni = reinterpret_cast<float4*>(blob + S.o_enrm_id)[g];
+        const m3 b = basis_fromz(xyz(ni));
+        reinterpret_cast<float4*>(blob + S.o_enrm)[g] = make_float4(b.c3.x, b.c3.y, b.c3.z, b.c1.x);
+        ni.w = b.c2.x;
+        blob[S.o_elems + g].w = __float_as_uint(b.c2.y);
+    }
+    const int nmat = (S.o_lights - S.o_materials) / 6;
+    for (int k = threadIdx.x; k < nmat; k += BLOCK) {
+        DMaterial& m = reinterpret_cast<DMaterial*>(blob + S.o_materials)[k];
+        const v3 c = V3(m.color[0], m.color[1], m.color[2]) / pif;
+        m.scattering[0] = c.x;
+        m.scattering[1] = c.y;
+        m.scattering[2] = c.z;
+    }
+}
+
 // HBM mode: the scene is read from global memory (L2/MALL-resident); stack in static LDS.
 // ADAPT (both kernels): the instance an adapted context launches (A.frozen is set), passed on to
 // trace_body_items. A template parameter here leaves every instance's ISA as it is; moving a
@@ -791,6 +826,7 @@ __global__ __launch_bounds__(BLOCK) JT_WAVES_PER_EU_F(F) void trace_kernel_lds(D
     __syncthreads();
     if constexpr (node_baked<OVF, false, WIDE, F>()) {
         bake_nodes(S, blob);
+        if constexpr (shade_baked<OVF, false, WIDE, F>()) bake_shading(S, blob);
         __syncthreads();
     }
     const DScene L = blob_scene(S, blob);

@@ -594,7 +594,10 @@ void flatten_instances(const jt_scene* scene, const jt_scene_bvh* bvh, HostScene
         const jt_bvh_tree& bt = bvh->blas[in.shape];
         const bool leaf_root = bt.nnodes > 0 && !bt.nodes[0].internal;
         hs.inst_blas[k] = make_int4(hs.wide ? hs.wroot[in.shape] : d.blas_root, ident ? 1 : 0, d.kind, in.shape | (leaf_root ? 1 << 30 : 0));
-        if (!ident) hs.feat |= FT_XFORM;
+        // a frame of -0 entries has an identity inverse under == and is not rot_identity: its element
+        // normals come from enrm through transform_normal (zero components may change sign), which
+        // the kernels without FT_XFORM do not keep (baked shading, jt_kernels.h bake_shading)
+        if (!ident || !rot_identity(fv)) hs.feat |= FT_XFORM;
         hs.inst_shade[k] = DInstShade{f4(fv[0], fv[1], fv[2], fv[3]), f4(fv[4], fv[5], fv[6], fv[7]), f4(fv[8], fv[9], fv[10], fv[11]),
                                       in.material, in.shape, scene->materials[in.material].type,
                                       rot_identity(fv) ? 1 : 0};

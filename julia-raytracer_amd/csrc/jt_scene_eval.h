@@ -201,10 +201,27 @@ struct Shading {
     v3 position, normal;
     MatPoint mat;
 };
+// Where the baked shading of a hit lies in the workgroup's LDS copy (bake_shading, jt_kernels.h,
+// names the bytes): kept as two indices and read at the use, not as nine floats across the bounce
+struct BakedShade {
+    int elem, material;  // global element, material
+};
+__device__ __forceinline__ BakedBasis baked_basis(const DScene& S, int g) {
+    const float4 bz = S.enrm[g], ni = S.enrm_id[g];
+    return BakedBasis{xyz(ni), bz.w, ni.w, __int_as_float(S.elems[g].w), xyz(bz)};
+}
+__device__ __forceinline__ v3 baked_color_pi(const DScene& S, int material) {
+    const DMaterial& m = S.materials[material];
+    return V3(m.scattering[0], m.scattering[1], m.scattering[2]);
+}
 
 // eval_shading_position + eval_shading_normal + eval_material (src/scene.jl:416-673)
-template <int F>
-__device__ __forceinline__ void eval_shading(const DScene& S, int inst, int elem, v2 uv, v3 outgoing, Shading& out) {
+// SB (the baking LDS-mode kernels, shade_baked: S is the workgroup's baked copy): the element's and
+// the material's baked shading are read where the bounce uses them (bk says where).
+template <int F, bool SB = false>
+__device__ __forceinline__ void eval_shading(const DScene& S, int inst, int elem, v2 uv, v3 outgoing, Shading& out,
+                                             BakedShade* bk = nullptr) {
+    static_assert(!SB || ft_none(F), "baked shading: the FT_NONE kernels only");
     const DInstShade is = S.inst_shade[inst];
     const DShape sh = S.shapes[is.shape];
     const int4 e = S.elems[sh.idx_base + elem];
@@ -221,6 +238,12 @@ __device__ __forceinline__ void eval_shading(const DScene& S, int inst, int elem
     v3 normal;
     if ((F & FT_TEX) && m.normal_tex >= 0) {
         normal = eval_normalmap(S, sh, e, f, m, uv);
+    } else if constexpr (SB) {
+        // a scene without FT_XFORM has only instances of rot_identity (layout_scene), so the element
+        // normal is enrm_id's; the bake pass (bake_shading) left the basis in the bytes around it
+        normal = xyz(S.enrm_id[sh.idx_base + elem]);
+        bk->elem = sh.idx_base + elem;
+        bk->material = is.material;
     } else if (!(F & FT_ATTR) || sh.nrm_base < 0) {
         normal = element_normal(S, is.rot_identity, f, sh.idx_base + elem);
     } else {
@@ -245,7 +268,8 @@ __device__ __forceinline__ void eval_shading(const DScene& S, int inst, int elem
     float roughness = m.roughness * roughness_tex.y;
     roughness = roughness * roughness;
     p.ior = m.ior;
-    p.scattering = V3(m.scattering[0], m.scattering[1], m.scattering[2]) * xyz(scattering_tex);
+    // (baked shading keeps color / pif in DMaterial::scattering: read by kernels with FT_VOL only)
+    p.scattering = SB ? V3(0, 0, 0) : V3(m.scattering[0], m.scattering[1], m.scattering[2]) * xyz(scattering_tex);
     p.scanisotropy = m.scanisotropy;
     p.trdepth = m.trdepth;
     if ((F & FT_VOL) && (mtype == M_REFRACTIVE || mtype == M_VOLUMETRIC || mtype == M_SUBSURFACE)) {

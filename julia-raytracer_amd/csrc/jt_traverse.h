@@ -99,6 +99,18 @@ __host__ __device__ constexpr bool node_baked() {
     return JT_NODE_BAKE && !OVF && !NCACHE && !WIDE && ft_none(F);
 }
 __host__ __device__ constexpr int push_bit(bool baked) { return baked ? BAKE_MASK_BIT : 0; }
+// Baked shading (jt_bsdf.h BakedBasis; bake_shading, jt_kernels.h): the same kernels' bake pass also
+// writes, per element of the LDS copy, the hemisphere basis of the element normal and, per material,
+// color / pi, into bytes of the copy that an FT_NONE kernel never reads; their matte bounce reads
+// them back instead of dividing. Every other kernel computes both per bounce, its code unchanged.
+// 0: the baking kernels compute them too (A/B runs).
+#ifndef JT_SHADE_BAKE
+#define JT_SHADE_BAKE 1
+#endif
+template <bool OVF, bool NCACHE, bool WIDE, int F>
+__host__ __device__ constexpr bool shade_baked() {
+    return JT_SHADE_BAKE && node_baked<OVF, NCACHE, WIDE, F>();
+}
 // Instance roots (jt_push.h): the bake pass also writes a baked copy of every instance's BLAS root
 // node into the LDS copy of inst_trav, and an instance's stack entry in a baking kernel is the
 // copy's node index, so node_step reads its node at the popped index for every entry type and has
