@@ -134,15 +134,32 @@ __device__ __forceinline__ m3 basis_baked(const BakedBasis& k, bool flip) {  // 
 // the headline kernel two spilled VGPRs and four more spilled SGPRs.
 // (sample_hemisphere_cos's lines are restated, not shared: routed through a common function, every
 // other kernel's register allocation changed)
+//
+// matte_local: sample_hemisphere_cos's local sample (r cos phi, r sin phi, z) of rn = two rand1f
+// values, each k * 2^-24. UNIT: the same floats from sincos_unit (jt_device.h) and sqrt_fast without
+// jl_sqrt's domain test: rn.y is 0 or at least 2^-24, and 1 - z * z lies in [2^-23, 1] for every
+// rn.y of the set (tests/sincos_unit_check.cpp enumerates it), inside the [2^-95, inf) on which
+// sqrt_fast is __builtin_sqrtf on every bit pattern (scripts/exhaustive/sqrt_check.hip). !UNIT:
+// sample_hemisphere_cos's own lines (JT_SINCOS_UNIT=0, and what tests/probe compares UNIT with).
+template <bool UNIT>
+__device__ __forceinline__ v3 matte_local(v2 rn) {
+    float z, r, s, c;
+    if constexpr (UNIT) {
+        z = rn.y == 0 ? 0.0f : sqrt_in_domain(rn.y);
+        r = sqrt_in_domain(1 - z * z);
+        sincos_unit(rn.x, &s, &c);
+    } else {
+        z = __builtin_sqrtf(rn.y);
+        r = __builtin_sqrtf(1 - z * z);
+        float phi = 2 * pif * rn.x;
+        jl_sincos(phi, &s, &c);
+    }
+    return V3(r * c, r * s, z);
+}
 template <class Load>
 __device__ __forceinline__ v3 sample_matte_baked(Load load, float roughness, v3 outgoing, v2 rn) {
     if (roughness == 0) return V3(0, 0, 0);
-    float z = __builtin_sqrtf(rn.y);
-    float r = __builtin_sqrtf(1 - z * z);
-    float phi = 2 * pif * rn.x;
-    float s, c;
-    jl_sincos(phi, &s, &c);
-    const v3 local = V3(r * c, r * s, z);
+    const v3 local = matte_local<JT_SINCOS_UNIT != 0>(rn);
     __asm__ volatile("" ::: "memory");
     const BakedBasis k = load();
     const bool flip = !(dot(k.n, outgoing) >= 0);  // eval_shading: normal = dot(n, o) >= 0 ? n : -n

@@ -106,6 +106,14 @@ __device__ __forceinline__ float jl_sqrt(float x) {
 #endif
     return __builtin_sqrtf(x);
 }
+// jl_sqrt without the domain test, for a caller that proves its x in [2^-95, inf) itself
+__device__ __forceinline__ float sqrt_in_domain(float x) {
+#if JT_SQRT_FORM
+    return sqrt_fast<JT_SQRT_FORM>(x);
+#else
+    return __builtin_sqrtf(x);
+#endif
+}
 __device__ __forceinline__ v3 normalize(v3 a) {  // src/math.jl:71-78
     float l = jl_sqrt(dot(a, a));
     return l != 0 ? a / l : a;
@@ -214,6 +222,53 @@ __device__ __forceinline__ float jl_cos(float x) {
     jl_sincos(x, &s, &c);
     return c;
 }
+// jl_sincos(2 * pif * u) for u = k * 2^-24, k = 0 .. 2^24 - 1 (every rand1f value), the same floats
+// in half the FP64 instructions, with no large-argument call and no branch: dsincos_small's
+// reduction and kernels with every multiply-add fused. The fused doubles differ from the unfused
+// ones in their last bits only, and no phi of the set lies within 4 double-ulps of a float rounding
+// midpoint (tests/test_primitives_host.py), so both round to the same float: "evaluated in double,
+// rounded once" (DESIGN.md §3). The quadrant rint(phi * invpio2) is (k + 2^21) >> 22 for every k;
+// the swap and the negation act on the rounded floats (round to nearest is sign-symmetric), as
+// 32-bit selects and XORs. tests/sincos_unit_check.cpp enumerates all 2^24 k on the host, and
+// tests/test_gpu_sincos_unit.py on the device. Only for such u: any other argument takes jl_sincos.
+// JT_SINCOS_UNIT: 0 no caller (A/B runs), 1 the baked matte sample (sample_matte_baked, jt_bsdf.h),
+// 2 the baking kernels' camera sample too (sample_disk_unit).
+#ifndef JT_SINCOS_UNIT
+#define JT_SINCOS_UNIT 2
+#endif
+// A constant of sincos_unit in a scalar register pair, made where it is used. Left to the compiler, the
+// fourteen doubles of the straight-line form are hoisted out of the sample loop into vector registers
+// (the headline kernel: 20 spilled VGPRs, reloaded every bounce); jl_sincos's are scalar moves
+// inside its branch.
+__device__ __forceinline__ double scalar_const(double c) {
+    __asm__ volatile("" : "+s"(c));
+    return c;
+}
+__device__ __forceinline__ void sincos_unit(float u, float* s, float* c) {
+#define JT_K(x) scalar_const(x)  // each where it is used: the barriers keep their order, so two or three pairs live at a time
+    const unsigned k = (unsigned)(u * 16777216.0f);
+    const unsigned nq = (k + (1u << 21)) >> 22;  // 0 .. 4
+    const double x = (double)(2 * pif * u), n = (double)nq;
+    double r = __builtin_fma(-n, JT_K(1.57079632673412561417e+00), x);  // pio2_1
+    r = __builtin_fma(-n, JT_K(6.07710050650619224932e-11), r);         // pio2_1t
+    const double z = r * r;
+    double sr = __builtin_fma(z, JT_K(1.58969099521155010221e-10), JT_K(-2.50507602534068634195e-08));  // S6, S5
+    sr = __builtin_fma(z, sr, JT_K(2.75573137070700676789e-06));                                         // S4
+    sr = __builtin_fma(z, sr, JT_K(-1.98412698298579493134e-04));                                        // S3
+    sr = __builtin_fma(z, sr, JT_K(8.33333333332248946124e-03));                                         // S2
+    const double ks = __builtin_fma(z * r, __builtin_fma(z, sr, JT_K(-1.66666666666666324348e-01)), r);  // S1
+    double cr = __builtin_fma(z, JT_K(-1.13596475577881948265e-11), JT_K(2.08757232129817482790e-09));  // C6, C5
+    cr = __builtin_fma(z, cr, JT_K(-2.75573143513906633035e-07));                                        // C4
+    cr = __builtin_fma(z, cr, JT_K(2.48015872894767294178e-05));                                         // C3
+    cr = __builtin_fma(z, cr, JT_K(-1.38888888888741095749e-03));                                        // C2
+    cr = z * __builtin_fma(z, cr, JT_K(4.16666666666666019037e-02));                                     // C1
+    const double kc = __builtin_fma(z, cr, __builtin_fma(-0.5, z, 1.0));
+#undef JT_K
+    const float sf = (float)ks, cf = (float)kc;
+    const bool odd = (nq & 1u) != 0;
+    *s = __uint_as_float(__float_as_uint(odd ? cf : sf) ^ ((nq & 2u) << 30));
+    *c = __uint_as_float(__float_as_uint(odd ? sf : cf) ^ (((nq + 1u) & 2u) << 30));
+}
 // atan in double (fdlibm s_atan.c), used by sample_microfacet on every rough specular sample
 __device__ __forceinline__ float jl_atan(float xf) {
     const double atanhi[4] = {4.63647609000806093515e-01, 7.85398163397448278999e-01, 9.82793723247329054082e-01,
@@ -265,6 +320,10 @@ __device__ __noinline__ float jl_exp(float x) { return (float)exp((double)x); }
 __device__ __forceinline__ float jl_sin(float x) { return sinf(x); }
 __device__ __forceinline__ float jl_cos(float x) { return cosf(x); }
 __device__ __forceinline__ void jl_sincos(float x, float* s, float* c) { sincosf(x, s, c); }
+#ifndef JT_SINCOS_UNIT
+#define JT_SINCOS_UNIT 0
+#endif
+__device__ __forceinline__ void sincos_unit(float u, float* s, float* c) { sincosf(2 * pif * u, s, c); }
 __device__ __forceinline__ float jl_atan(float x) { return atanf(x); }
 __device__ __forceinline__ float jl_atan2(float y, float x) { return atan2f(y, x); }
 __device__ __forceinline__ float jl_acos(float x) { return acosf(x); }
@@ -340,6 +399,13 @@ __device__ __forceinline__ v2 sample_disk(v2 ruv) {  // src/sampling.jl:12-16
     float phi = 2 * pif * ruv.x;
     float s, c;
     jl_sincos(phi, &s, &c);
+    return V2(c * r, s * r);
+}
+// sample_disk for a ruv.x of rand1f's set (the baking kernels' camera sample): the same floats
+__device__ __forceinline__ v2 sample_disk_unit(v2 ruv) {
+    float r = jl_sqrt(ruv.y);
+    float s, c;
+    sincos_unit(ruv.x, &s, &c);
     return V2(c * r, s * r);
 }
 // With aperture == +0, eval_camera reads sample_disk's result only through lens_uv * 0, i.e.

@@ -575,7 +575,10 @@ __device__ __forceinline__ void eval_camera(const DCamera& cam, v2 image_uv, v2 
 }
 
 // sample_camera (src/trace.jl:651-674) after the prologue's 4 draws (:597-608): the camera ray of
-// pixel (i, j) from an rng at the start of the sample's stream (also camera_kernel, jt_surface.hip)
+// pixel (i, j) from an rng at the start of the sample's stream (also camera_kernel, jt_surface.hip).
+// UNIT (the baking kernels with JT_SINCOS_UNIT=2): the lens sample's azimuth through sincos_unit, the
+// same floats; luv.x is a rand1f value
+template <bool UNIT = false>
 __device__ __forceinline__ void camera_sample(const DParams& P, int i, int j, Rng& rng, v3& o, v3& d) {
     v2 puv = rand2f(rng);
     v2 luv = rand2f(rng);
@@ -588,14 +591,14 @@ __device__ __forceinline__ void camera_sample(const DParams& P, int i, int j, Rn
                     width * (puv.y < 0.5f ? __builtin_sqrtf(2 * puv.y) - 1 : 1 - __builtin_sqrtf(2 - 2 * puv.y)) + offset);
         uv = V2(((float)i + fuv.x) / (float)P.width, ((float)j + fuv.y) / (float)P.height);
     }
-    eval_camera(P.cam, uv, P.cam.pinhole ? sample_disk_signs(luv) : sample_disk(luv), o, d);
+    eval_camera(P.cam, uv, P.cam.pinhole ? sample_disk_signs(luv) : (UNIT ? sample_disk_unit(luv) : sample_disk(luv)), o, d);
 }
 
 // trace_sample prologue (src/trace.jl:597-608): 4 draws, camera ray
-template <int F>
+template <int F, bool UNIT = false>
 __device__ __forceinline__ void start_path(const DParams& P, int i, int j, int pixel, int sample, Path& st) {
     st.rng = rng_init(P.seed, pixel, sample);
-    camera_sample(P, i, j, st.rng, st.o, st.d);
+    camera_sample<UNIT>(P, i, j, st.rng, st.o, st.d);
     st.set_radiance<F>(V3(0, 0, 0));
     st.set_weight<F>(V3(1, 1, 1));
     st.set_max_roughness<F>(0.0f);

@@ -435,7 +435,7 @@ __device__ __forceinline__ void trace_body_items(const DScene& S0, const DParams
             const DParams& P = karg_params<karg_params_on<SAMPLER, F>()>(P0);
             const int i = item_coords<F>() ? item_i(item) : tpixel % P.width;
             const int j = item_coords<F>() ? item_j(item) : tpixel / P.width;
-            start_path<F>(P, i, j, item_coords<F>() ? j * P.width + i : tpixel, sample, st);
+            start_path<F, SB && JT_SINCOS_UNIT >= 2>(P, i, j, item_coords<F>() ? j * P.width + i : tpixel, sample, st);
             query_start<WIDE>(S, T, st.o, st.d, -1, stack, 0, PB);
             if (!WC) lds_count(1, true);
             if constexpr (item_first_pop<WIDE, F>()) {
